@@ -2,6 +2,7 @@
 configs (BASELINE.json), MI355X-native HIP path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ncf|lightgcn|lightgcn128|widedeep|mf|ncf_deep]
+                    [--dump-outputs DIR] [--full]
 
 Default workload = BASELINE.json configs[1]: NeuralCF mf 64, mlp [128,64,32], full H&M
 shape (1,371,980 users x 105,542 items), batch 4096 users per rank per step, K=12,
@@ -14,12 +15,19 @@ resident in HBM before timing.
 N>1 (torchrun, one rank per GPU): items are row-sharded across ranks; every rank brings
 4096 users and scores all N*4096 users against its I/N items (weak scaling).
 
-Also printed in the same JSON line:
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs
+(--dump-outputs DIR: DIR/scores.npy float32 [B, 12] and DIR/items.npy float64 [B, 12], the
+arrays `recommend()` returned; the inputs are seeded, so two builds compare output for output)
+and prints ONE JSON line: metric, value, ms_per_step, dtype and
   roofline     -- dominant kernel (NCF: ncf16_scan_kernel, the certified f16 scan; with
                   --exact the fp32 ncf32_kernel) algorithmic FLOPs per launch / its
                   average duration (HIP events on the ctx stream, measured live here),
                   vs the MFMA peak of the kernel's dtype; `traffic` from the committed
                   rocprofv3 PMC summary (profiles/) when present for this workload.
+With --full the same line also carries the legs measured after the timed region (exact_fp32,
+filtered, module_surface, pipelined_3_streams, prefilter counters, ...), and the default NCF
+run adds every other workload's line, the pruning-robustness lines and the B = 1 serve
+latencies, each from a child process:
   exact_fp32   -- the same step with the pre-filter off (every pair in exact fp32).
   cpu_baseline -- the reference's PyTorch-CPU path (oracle/torch_cpu.py: its torch ops
                   restated, pinned to the reference goldens) on a bounded user sample,
@@ -258,6 +266,16 @@ def build_workload(name, rank, world, device, batch, exact=False, weights="init"
     ret = dict(step=rec.recommend, per_launch=per_launch, bound=bound, kernel=kernel,
                timing=_lib.TIME_SCORE)
     return ret, info, cpu
+
+
+def dump_outputs(path, out, rank):
+    """--dump-outputs: the (scores, items) pair the last timed step returned, as float32 /
+    float64 .npy files (item ids are exact in float64); a few hundred KB at the default batch."""
+    vals, idx = out
+    os.makedirs(path, exist_ok=True)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    np.save(os.path.join(path, f"scores{tag}.npy"), vals.detach().float().cpu().numpy())
+    np.save(os.path.join(path, f"items{tag}.npy"), idx.detach().cpu().numpy().astype(np.float64))
 
 
 def timed_rate(fn, batches, steps, world, B):
@@ -542,6 +560,9 @@ def compact_line(line):
 # where one host hiccup moved a whole line by 60 % (gpurun_out/r11x); their extra lines time
 # at least 200 steps
 SHORT_STEP_WORKLOADS = ("mf",)
+# a headline timed over thousands of steps does not lengthen the child lines with it (ncf_deep:
+# 24 ms a step): each times at most this many, and reports its own `steps`
+EXTRA_MAX_STEPS = 1000
 
 
 def run_extras(args):
@@ -552,10 +573,12 @@ def run_extras(args):
     configs[2] (lightgcn) last, right above the headline, so a tail of the output keeps it."""
     out, lat, full = {}, {}, {}
     for w, what in EXTRA_WORKLOADS:
-        steps, warmup = (5, 1) if w == "widedeep" else (args.steps, args.warmup)
+        steps, warmup = ((5, 1) if w == "widedeep" else
+                         (min(args.steps, EXTRA_MAX_STEPS), args.warmup))
         if w in SHORT_STEP_WORKLOADS:  # sub-ms steps: a longer timed region (host jitter)
             steps, warmup = max(steps, 200), max(warmup, 20)
-        argv = ["--workload", w, "--steps", str(steps), "--warmup", str(warmup), "--no-extras"]
+        argv = ["--workload", w, "--steps", str(steps), "--warmup", str(warmup), "--full",
+                "--no-extras"]
         if args.no_cpu_baseline:
             argv.append("--no-cpu-baseline")
         t0 = time.perf_counter()
@@ -573,7 +596,7 @@ def run_extras(args):
                   ("mf", ("norms", "student_t")), ("ncf_deep", ("norms",))):
         for wt in ws:
             wname, _, opt = wt.partition("+")
-            st, wu = args.steps, args.warmup
+            st, wu = min(args.steps, EXTRA_MAX_STEPS), args.warmup
             if w in SHORT_STEP_WORKLOADS:
                 st, wu = max(st, 200), max(wu, 20)
             line = run_child(["--workload", w, "--weights", wname, "--steps", str(st),
@@ -625,10 +648,22 @@ def main():
                     help="the headline timed loop only (no exact / filtered / module-surface / "
                          "pipelined / baseline legs): what the rocprofv3 kernel stats in "
                          "profiles/ are collected over, so their averages match `roofline`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the benchmark "
+                         "reports: exact fp32 / filtered / module-surface / pipelined legs, the "
+                         "pre-filter counters, the CPU baseline and (default NCF run) the other "
+                         "workloads, pruning robustness and B=1 serve latencies.  Without it: "
+                         "set up, warm up, time --steps steps, print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/scores.npy (float32) "
+                         "and DIR/items.npy (float64), [batch, 12] each (rank r > 0 of a "
+                         "multi-GPU run: scores_rank<r>.npy / items_rank<r>.npy)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="default NCF run only: skip the other workloads' lines and the B=1 "
+                    help="--full, default NCF run only: skip the other workloads' lines and the B=1 "
                          "serve latencies (otherwise measured after the headline, N=1 only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
 
@@ -662,21 +697,30 @@ def main():
     _lib.enable_timing(device, wl["timing"])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for j in range(args.steps):
-        step(batches[j % nb])
+        last = step(batches[j % nb])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     ktime_ms, launches = _lib.kernel_timing(device)
     _lib.enable_timing(device, False)
-    # pre-filter counters from one extra, untimed step (counting uses atomics)
-    _lib.prefilter_stats(device, reset=True)
-    _lib.set_option(device, _lib.HNM_OPT_STATS, 1)
-    step(batches[0])
-    _lib.set_option(device, _lib.HNM_OPT_STATS, 0)
-    pf_rows, pf_cands, pf_fallback, pf_sampled = _lib.prefilter_stats(device, reset=True,
-                                                                      extended=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank)
+    del last
+    # the legs measured beside the headline: --full only, and never with --profile-only
+    legs = args.full and not args.profile_only
+    pf_rows = pf_cands = pf_fallback = pf_sampled = 0
+    if args.full or args.profile_only or info.get("_deep_cert"):
+        # pre-filter counters from one extra, untimed step (counting uses atomics); a plain run
+        # takes it only for the deep tower, whose kernel and dtype fields depend on it
+        _lib.prefilter_stats(device, reset=True)
+        _lib.set_option(device, _lib.HNM_OPT_STATS, 1)
+        step(batches[0])
+        _lib.set_option(device, _lib.HNM_OPT_STATS, 0)
+        pf_rows, pf_cands, pf_fallback, pf_sampled = _lib.prefilter_stats(device, reset=True,
+                                                                          extended=True)
     exact_rate = None
     if info.get("_deep_cert") and pf_rows and pf_fallback < pf_rows:
         # round 6: the deep tower's certified f16 pre-filter pruned (trained-like weights): the
@@ -688,10 +732,10 @@ def main():
     elif info.get("_deep_cert") and pf_rows:
         info["scan"] += ("; certified pre-filter tried: its proxy rows predict no pruning at these "
                          "weights (worst-case bound wider than the score spread), exact kernels ran")
-    if args.profile_only:
+    if not legs:
         args.no_extras = args.no_cpu_baseline = True
     per_pair = None
-    if info.get("_per_pair_route") and not args.profile_only:
+    if info.get("_per_pair_route") and legs:
         # the same step through the per-pair LDS kernel + dense rows + row top-k
         # (HNM_OPT_DEEP_MFMA = 0, bitwise the same lists), reported beside `value`
         _lib.set_option(device, _lib.HNM_OPT_DEEP_MFMA, 0)
@@ -703,7 +747,7 @@ def main():
         torch.cuda.synchronize()
         per_pair = B * 2 / (time.perf_counter() - tp)
         _lib.set_option(device, _lib.HNM_OPT_DEEP_MFMA, 1)
-    if not args.exact and not args.profile_only and not info.get("_per_pair_route"):
+    if legs and not args.exact and not info.get("_per_pair_route"):
         # the like-for-like fp32 path (HNM_OPT_PREFILTER=0: every pair scored in exact fp32
         # arithmetic), timed the same way on the same batches, reported beside `value`
         _lib.set_prefilter(device, False)
@@ -795,7 +839,7 @@ def main():
         # `frac` against perfect L2 locality, `vs_uniform_random` against the same gathers in
         # random order (what the walks' column order buys)
         line["roofline"]["gather_ceiling"] = gather_ceiling(wl["gathered"], avg_kernel_ms)
-    if "_serving" in info and rank == 0 and world == 1 and not args.profile_only:
+    if "_serving" in info and rank == 0 and world == 1 and legs:
         # serving rate with the propagation computed once (weights unchanged between calls);
         # reported beside `value`, never as it
         serve = info["_serving"]()
@@ -812,7 +856,7 @@ def main():
             "value": round(B * world * exact_rate[1] / exact_rate[0], 2), "unit": "users/s",
             "steps": exact_rate[1],
             "note": "same step with HNM_OPT_PREFILTER=0: every (user, item) pair in exact fp32"}
-    if "_filtered" in info and not args.exact and not args.profile_only:
+    if "_filtered" in info and not args.exact and legs:
         # purchase-history filter (the reference's filter_items / serve.py:350-352): every
         # user's history = its interactions in the synthetic H&M transactions (the LightGCN
         # graph's edges, mean 23.2 items), held on the device as a UserHistory; each step
@@ -858,7 +902,7 @@ def main():
             line["module_surface"] = out
         del hist
     if (world == 1 and args.workload in ("ncf", "mf", "lightgcn") and not args.exact
-            and not args.profile_only):
+            and legs):
         # serving throughput with independent batches overlapped on 3 HIP streams (the small
         # per-call kernels and re-scoring of one batch run beside another batch's scan);
         # reported beside `value` (one batch in flight), never as it
@@ -872,7 +916,7 @@ def main():
                         "recommend() calls on independent batches; what a threaded server gets"}
         except Exception as e:  # reported, never fatal
             log(f"pipelined leg failed: {e!r}")
-    if world > 1 and "_user_sharded" in info and not args.profile_only:
+    if world > 1 and "_user_sharded" in info and legs:
         # SURVEY §8(e)'s comparison layout: every rank holds the whole catalogue and scores
         # only its own B users (no collective); the same batches, clock and max over ranks
         try:
@@ -886,7 +930,7 @@ def main():
             del us
         except Exception as e:  # reported, never fatal
             log(f"user-sharded leg failed: {e!r}")
-    if "_full_step" in info and not args.profile_only:
+    if "_full_step" in info and legs:
         full = info["_full_step"]
         full(batches[0])
         torch.cuda.synchronize()

@@ -25,9 +25,11 @@ into the reference modules via load_state_dict; outputs are stored as small .npz
 from __future__ import annotations
 
 import inspect
+import io
 import os
 import sys
 import types
+import zipfile
 
 import numpy as np
 import torch
@@ -127,8 +129,14 @@ def tagged_users(U, B, seed):
 
 
 def save(name, **arrs):
+    # an .npz whose members are LZMA-compressed (np.load reads it like any other): deflate
+    # leaves lightgcn_d128.npz, mostly random fp32 tables, above 1 MiB
     path = os.path.join(HERE, name)
-    np.savez_compressed(path, **arrs)
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for k, v in arrs.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            z.writestr(k + ".npy", buf.getvalue())
     print(f"wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
 
 

@@ -1,5 +1,5 @@
-"""CPU: bench.py's headline line stays inside a driver's 8 KB output tail.  The default run
-prints each workload's full line first (`workload_line <w> {...}`) and then ONE headline JSON
+"""CPU: bench.py's headline line stays inside a driver's 8 KB output tail.  The default
+`--full` run prints each workload's full line first (`workload_line <w> {...}`) and then ONE headline JSON
 line whose `other_configs` repeats every workload compactly (VERDICT r3 "Weak #1": a cut tail
 had lost configs[2]).  Checked on the round's recorded default line (profiles/) and on a
 compacted synthetic line carrying every field compact_line keeps."""

@@ -24,7 +24,7 @@ else
   step tests 1000 python -u -m pytest tests -x -v -m gpu --timeout 180 --timeout-method thread
 fi
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench_ncf 900 python bench.py
+step bench_ncf 900 python bench.py --full
 export HNM_DIST_BACKEND=gloo
-step bench_2rank 400 python bench.py --gpus 2 --workload lightgcn128 --steps 5 --warmup 2
+step bench_2rank 400 python bench.py --gpus 2 --workload lightgcn128 --steps 5 --warmup 2 --full
 echo ok

@@ -20,9 +20,9 @@ step() {  # name timeout cmd...
   tail -c 600 "$OUT/$name.out"; echo
 }
 step tests 1000 python -u -m pytest tests -x -v -m gpu --timeout 180 --timeout-method thread
-step bench_default 900 python bench.py
-step bench_ncf_personal 300 python bench.py --weights personal --no-cpu-baseline
-HNM_DIST_BACKEND=gloo step bench_2rank 400 python bench.py --gpus 2 --workload lightgcn128 --steps 5 --warmup 2
+step bench_default 900 python bench.py --full
+step bench_ncf_personal 300 python bench.py --weights personal --full --no-cpu-baseline
+HNM_DIST_BACKEND=gloo step bench_2rank 400 python bench.py --gpus 2 --workload lightgcn128 --steps 5 --warmup 2 --full
 if [ -n "$PROF" ]; then
   cd /tmp && export TMPDIR=/tmp
   for w in ncf lightgcn widedeep mf ncf_deep; do

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/$1; W=$2; PAT=$3; ARGS=$4; shift 4
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for t in "$@"; do
-  HNM_LIB_PATH=$ROOT/tools/bin/libhnm_$t.so timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$t -o k -- python3 $ROOT/bench.py --workload $W $ARGS --no-cpu-baseline --no-extras > $OUT/$t.log 2>&1 || { echo "variant $t failed"; tail -5 $OUT/$t.log; exit 1; }
+  HNM_LIB_PATH=$ROOT/tools/bin/libhnm_$t.so timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$t -o k -- python3 $ROOT/bench.py --workload $W $ARGS --full --no-cpu-baseline --no-extras > $OUT/$t.log 2>&1 || { echo "variant $t failed"; tail -5 $OUT/$t.log; exit 1; }
   f=$(find $OUT/$t -name 'k_kernel_stats.csv' | head -1)
   python3 - "$f" "$PAT" "$t" <<'PY'
 import csv, re, sys

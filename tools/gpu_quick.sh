@@ -14,6 +14,6 @@ if [ -n "$KEXPR" ]; then
   tail -1 $OUT/tests.out
 fi
 for w in $WLS; do
-  timeout -k 10 300 python bench.py --workload $w --no-cpu-baseline > $OUT/bench_$w.out 2> $OUT/bench_$w.err || { tail -20 $OUT/bench_$w.err; exit 1; }
+  timeout -k 10 300 python bench.py --workload $w --full --no-cpu-baseline > $OUT/bench_$w.out 2> $OUT/bench_$w.err || { tail -20 $OUT/bench_$w.err; exit 1; }
   python -c "import json; d=json.loads(open('$OUT/bench_$w.out').read().strip().splitlines()[-1]); print('$w', d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['avg_kernel_ms'], d['roofline']['frac'], d.get('prefilter'))"
 done

@@ -1,6 +1,6 @@
 set -uo pipefail
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/r7m; mkdir -p $OUT
-HNM_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --workload lightgcn128 --steps 5 --warmup 2 > $OUT/bench_2rank.out 2> $OUT/bench_2rank.err || { echo 2rank failed; tail -20 $OUT/bench_2rank.err; exit 1; }
+HNM_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --workload lightgcn128 --steps 5 --warmup 2 --full > $OUT/bench_2rank.out 2> $OUT/bench_2rank.err || { echo 2rank failed; tail -20 $OUT/bench_2rank.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 for w in ncf lightgcn widedeep mf ncf_deep; do
   extra=""

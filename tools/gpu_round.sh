@@ -19,8 +19,8 @@ step() {  # name timeout cmd...   (stops the session on anything but success / t
 }
 step tests 1100 python -u -m pytest tests -v -m gpu --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench_default 900 python bench.py
-HNM_DIST_BACKEND=gloo step bench_2rank 400 python bench.py --gpus 2 --workload lightgcn128 --steps 5 --warmup 2
+step bench_default 900 python bench.py --full
+HNM_DIST_BACKEND=gloo step bench_2rank 400 python bench.py --gpus 2 --workload lightgcn128 --steps 5 --warmup 2 --full
 cd /tmp && export TMPDIR=/tmp
 for w in ncf lightgcn lightgcn128 widedeep mf; do
   extra=""

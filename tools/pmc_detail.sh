@@ -7,7 +7,7 @@ W=${1:-ncf}; OUT=${2:-gpurun_out/pmcd}; shift 2 || true
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p "$ROOT/$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--workload $W --steps 2 --warmup 1 --no-cpu-baseline $*"
+ARGS="--workload $W --steps 2 --warmup 1 --full --no-cpu-baseline $*"
 i=0
 for grp in "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_INSTS_BRANCH SQ_LDS_IDX_ACTIVE SQ_INST_LEVEL_LDS SQ_WAVES" \
            "SQ_VALU_MFMA_COEXEC_CYCLES SQ_IFETCH SQ_IFETCH_LEVEL SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_INST_CYCLES_SALU SQ_INSTS_SMEM SQ_WAVES" \
