@@ -108,6 +108,7 @@ _SIGS = {
                                      _p, _p]),
     "hnm_ncf_deep_prefilter_debug_f32": (_i32, [_p, C.POINTER(NcfDeepWeights), _p, _i64, _p,
                                                 _i64, _p]),
+    "hnm_ncf_deep_route": (_i32, [_p, C.POINTER(NcfDeepWeights), C.POINTER(C.c_int)]),
     "hnm_ncf_pair_scores_f32": (_i32, [_p, C.POINTER(NcfWeights), _p, _p, _i64, _p]),
     "hnm_ncf_prefilter_debug_f32": (_i32, [_p, C.POINTER(NcfWeights), _p, _i64, _p, _i64, _p]),
     "hnm_topk_merge_f32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i64, C.c_int, C.c_int, _p, _p]),

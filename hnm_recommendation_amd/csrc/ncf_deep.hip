@@ -8,7 +8,7 @@
 //   score = sum_j wp[j] g_u[j] g_i[j] + sum_j wp[mf + j] x_L[j] + bp (neural_cf.py:131-141),
 //   ONE fmaf chain in that order.
 // Two kernels compute it, bitwise alike:
-//   * ncf_deep_mfma_kernel (widths <= 64, mf <= 128): 32-item tiles through f32 MFMA chains,
+//   * ncf_deep_mfma_kernel (widths <= 128, mf <= 128): 32-item tiles through f32 MFMA chains,
 //     dense rows or fused per-partition top-k lists (hnm_ncf_deep_topk_f32) -- see below;
 //   * ncf_deep_kernel (any width <= 512, and the pair forward): per pair, a workgroup holds TP
 //     pairs' activations in LDS (k-major, so the TP lanes of a pair group read consecutive
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void ncf_deep_kernel(DeepArgs a, int maxw, uns
 }
 
 // ------------------------------------------------------------------ fp32-MFMA tower tiles
-// Towers whose widths dims[1..nl] are all <= 64 (and mf <= 128): every layer after the first is
+// Towers whose widths dims[1..nl] are all <= 128 (and mf <= 128): every layer after the first is
 // a chain of v_mfma_f32_32x32x2f32 over 32-item tiles -- A = the layer's weights (32 output
 // units x 2 k), B = the pairs' activations (2 k x 32 items).  The f32 MFMA accumulates each
 // output as the fmaf chain over k in order (MI355X_MICROARCH.md: exact f32, bitwise the chain),
@@ -136,14 +136,30 @@ __global__ __launch_bounds__(256) void ncf_deep_kernel(DeepArgs a, int maxw, uns
 //     partition; the 32-item tile (Q rows, GMF rows) is staged once in LDS for all 4 WU users;
 //   * top-k: a wave-resident list per (user, partition), merged across partitions afterwards
 //     (the exact NCF path's scheme, ncf.hip); DENSE writes the score rows instead.
-#define DM_W 64               // P / Q row width (pair-permuted, zero padded)
-#define DM_QRS (DM_W + 4)     // LDS row stride of the Q tile (b128 reads conflict-free)
+// Instantiations <W, NT>: W = the P / Q row width (pair-permuted, zero padded), NT = the 32-unit
+// tiles of the widest MFMA layer.
+//   * W = 64, NT = 1 or 2: towers of widths <= 64.  Both users' chains advance together (the
+//     two-chain body); three / two workgroups a CU.
+//   * W = 128, NT = 2 or 4: towers with a layer of 65..128 units (NT = 4: an MFMA layer's
+//     outputs).  The Q tile row stride W + 4 keeps the b128 reads conflict-free (132 mod 32 =
+//     4).  Two chains of four tiles would hold 2 x 4 x 16 accumulators for a layer's outputs and
+//     as many for its inputs (256 registers), so these run the two users' chains one after the
+//     other (the one-chain body: user A's last-layer units wait in registers for user B's, then
+//     the same prediction stage) as one workgroup a CU on the unified 512-register file, with
+//     no scratch; a weight image of 32..136 KB leaves room for one or two workgroups anyway.
 #define DM_WU 4               // users per wave (two MFMA chains at a time)
 #define DM_NU (4 * DM_WU)     // users per workgroup
 
+// workgroups a CU of an instantiation (its launch bound, and choose_partition's target)
+__host__ __device__ constexpr int dm_occ(int w, int nt) {
+  return w == 64 && nt <= 2 ? (nt == 1 ? 3 : 2) : 1;
+}
+// floats of the LDS copy of wp's MLP part: a single Linear's W units, or the last layer's tiles
+__host__ __device__ constexpr int dm_wpn(int w, int nt) { return w > 32 * nt ? w : 32 * nt; }
+
 struct DeepMArgs {
-  const float* P;      // [B, 64]
-  const float* Q;      // [I, 64]
+  const float* P;      // [B, W]
+  const float* Q;      // [I, W]
   const float* gu;     // gmf_user [num_users, mf]
   const float* G;      // [I, MFP] GMF item rows, zero padded, 16-B aligned
   const int64_t* uids;
@@ -153,7 +169,8 @@ struct DeepMArgs {
   int64_t num_users, num_items, B, ipp;
   int mf, nl, dl, img_n;
   int last16;   // the last layer (l = nl - 1 >= 2, <= 16 outputs) on v_mfma_f32_16x16x4f32
-  int meta[8];  // MFMA layer l >= 1: A image offset | 4-step groups << 16 | 32-unit tiles << 20
+  // MFMA layer l >= 1: A image offset (< 2^16) | 4-step groups (<= 16) << 16 | 32-unit tiles << 21
+  int meta[8];
   const int64_t* mptr;
   const int32_t* midx;
   int K;
@@ -221,19 +238,36 @@ __global__ __launch_bounds__(256) void deep_pack_kernel(DeepPack pk, float* __re
     }                                                     \
   } while (0)
 #define DM_ACC(W0, W1, BA, BB) DM_STEP(W0, W1, BA, BB, cA0, cA1, cB0, cB1)
+// The one-chain body (W = 128).  A operands of 4-step group S4 of a layer, one float4
+// a tile (tiles past the layer's nt: not read, not multiplied)
+#define DM1_LOADW(S4)                                                                           \
+  _Pragma("unroll") for (int t = 0; t < NT; ++t)                                                \
+    w[t] = (t == 0 || t < nt) ? *reinterpret_cast<const float4*>(A0 + (t * ks4 + (S4)) * 256)   \
+                              : make_float4(0.f, 0.f, 0.f, 0.f)
+// c[t] = W_l (tile t, component C of w[t]) x BV + (Z ? 0 : c[t]) for one k step
+#define DM1_STEP(C, BV, Z)                                                          \
+  do {                                                                              \
+    const float bv_ = (BV);                                                         \
+    _Pragma("unroll") for (int t = 0; t < NT; ++t)                                  \
+      if (t == 0 || t < nt) c[t] = mfma32x32x2(w[t].C, bv_, (Z) ? zero16 : c[t]);   \
+  } while (0)
 
-template <int NT, int MFP, bool DENSE>
-__global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(DeepMArgs a) {
+template <int W, int NT, int MFP, bool DENSE>
+__global__ __launch_bounds__(256, dm_occ(W, NT)) void ncf_deep_mfma_kernel(DeepMArgs a) {
+  static_assert((W == 64 && NT <= 2) || (W == 128 && (NT == 2 || NT == 4)), "see above");
   constexpr int WU = DM_WU, NU = DM_NU;
+  constexpr int QRS = W + 4;        // LDS row stride of the Q tile (b128 reads conflict-free)
+  constexpr int QF4 = W / 32;        // Q tile float4 a thread (32 rows x W / 4)
   constexpr int GRS = MFP + 4;       // LDS row stride of the GMF tile
   constexpr int GF4 = MFP / 32;      // GMF tile float4 a thread (32 rows x MFP / 4)
+  constexpr int WPN = dm_wpn(W, NT);
   extern __shared__ float4 dm_lds4[];
   float* img = (float*)dm_lds4;
-  float* qs = img + a.img_n;              // [TILE][DM_QRS] (one buffer: three workgroups a CU)
-  float* gs = qs + TILE * DM_QRS;         // [TILE][GRS]
-  float* ps = gs + TILE * GRS;            // [NU][DM_W]
-  float* us = ps + NU * DM_W;             // [NU][MFP]  g_u rows (zero padded)
-  float* wps = us + NU * MFP;             // [MFP + 64] wp: GMF part, MLP part (zero padded)
+  float* qs = img + a.img_n;              // [TILE][QRS] (one buffer: three workgroups a CU)
+  float* gs = qs + TILE * QRS;            // [TILE][GRS]
+  float* ps = gs + TILE * GRS;            // [NU][W]
+  float* us = ps + NU * W;                // [NU][MFP]  g_u rows (zero padded)
+  float* wps = us + NU * MFP;             // [MFP + WPN] wp: GMF part, MLP part (zero padded)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, j = lane & 31;
@@ -244,10 +278,10 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(Dee
   const int64_t part_end = std::min<int64_t>(I, part_start + a.ipp);
 
   for (int e = tid; e < a.img_n / 4; e += 256) dm_lds4[e] = reinterpret_cast<const float4*>(a.img)[e];
-  for (int e = tid; e < NU * DM_W / 4; e += 256) {
-    const int64_t b = ublk + e / (DM_W / 4);
+  for (int e = tid; e < NU * W / 4; e += 256) {
+    const int64_t b = ublk + e / (W / 4);
     reinterpret_cast<float4*>(ps)[e] =
-        b < B ? reinterpret_cast<const float4*>(a.P + b * DM_W)[e % (DM_W / 4)]
+        b < B ? reinterpret_cast<const float4*>(a.P + b * W)[e % (W / 4)]
               : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   for (int e = tid; e < NU * MFP; e += 256) {
@@ -256,7 +290,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(Dee
     const int64_t u = b < B ? a.uids[b] : -1;
     us[e] = (u >= 0 && u < a.num_users && c < a.mf) ? a.gu[u * a.mf + c] : 0.f;
   }
-  for (int e = tid; e < MFP + 64; e += 256)
+  for (int e = tid; e < MFP + WPN; e += 256)
     wps[e] = e < a.mf ? a.wp[e] : (e >= MFP && e - MFP < a.dl) ? a.wp[a.mf + e - MFP] : 0.f;
 
   WaveTopK<1> L[WU];
@@ -282,13 +316,13 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(Dee
 
   // item tile staging through registers: issued before a tile's compute, written to the other
   // LDS buffer after it
-  float4 qst[2], gst[GF4];
+  float4 qst[QF4], gst[GF4];
   auto load_tile = [&](int64_t base) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
+    for (int q = 0; q < QF4; ++q) {
       const int f = tid + 256 * q;
-      const int64_t item = base + (f >> 4);
-      qst[q] = item < part_end ? reinterpret_cast<const float4*>(a.Q + item * DM_W)[f & 15]
+      const int64_t item = base + f / (W / 4);
+      qst[q] = item < part_end ? reinterpret_cast<const float4*>(a.Q + item * W)[f % (W / 4)]
                                : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
@@ -301,9 +335,9 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(Dee
   };
   auto store_tile = [&](int buf) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
+    for (int q = 0; q < QF4; ++q) {
       const int f = tid + 256 * q;
-      *reinterpret_cast<float4*>(&qs[(buf * TILE + (f >> 4)) * DM_QRS + 4 * (f & 15)]) = qst[q];
+      *reinterpret_cast<float4*>(&qs[(buf * TILE + f / (W / 4)) * QRS + 4 * (f % (W / 4))]) = qst[q];
     }
 #pragma unroll
     for (int q = 0; q < GF4; ++q) {
@@ -329,7 +363,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(Dee
     const int buf = 0;
     const int64_t base = part_start + tt * TILE;
     if (tt + 1 < ntiles) load_tile(base + TILE);
-    const float* qrow = &qs[(buf * TILE + j) * DM_QRS];
+    const float* qrow = &qs[(buf * TILE + j) * QRS];
     const float* grow = &gs[(buf * TILE + j) * GRS];
     const int64_t item = base + j;
     const bool ivalid = item < part_end;
@@ -360,20 +394,21 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(Dee
 #pragma unroll
         for (int g = 0; g < MFP / 8; ++g) gmf8(g);
         // single Linear: the MLP output is relu(P + Q) itself, unit jj at pair-permuted column
-        const float* pr = &ps[(h ? urB : urA) * DM_W];
+        const float* pr = &ps[(h ? urB : urA) * W];
         for (int jj = 0; jj < a.dl; ++jj) {
-          const int c = (jj & 1) * (DM_W / 2) + (jj >> 1);
+          const int c = (jj & 1) * (W / 2) + (jj >> 1);
           s = fmaf(wm[jj], fmaxf(pr[c] + qrow[c], 0.f), s);
         }
-      } else {
+      } else if constexpr (W == 64) {
+        // the two-chain body (widths <= 64: at most 8 4-step groups a layer, so 4 bits of meta)
         // layer 2 (the first MFMA layer): B operand relu(P + Q) from the LDS tile
         f32x16 cA0, cA1, cB0, cB1;
         {
-          const float* pA = &ps[urA * DM_W + h * (DM_W / 2)];
-          const float* pB = &ps[urB * DM_W + h * (DM_W / 2)];
-          const float* qh = qrow + h * (DM_W / 2);
+          const float* pA = &ps[urA * W + h * (W / 2)];
+          const float* pB = &ps[urB * W + h * (W / 2)];
+          const float* qh = qrow + h * (W / 2);
           const int ks4 = (meta1 >> 16) & 15;
-          const bool two = NT > 1 && (meta1 >> 20) > 1;
+          const bool two = NT > 1 && (meta1 >> 21) > 1;
           const float* A0 = img + (meta1 & 0xffff) + 4 * lane;
           const float* A1 = A0 + ks4 * 256;
           const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -406,7 +441,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(Dee
         }
         f32x16 xA0, xA1, xB0, xB1;
         auto epilogue = [&](int meta) {  // x = relu(acc + b): fmaxf(acc + b, 0), the chain's
-          const int ks4 = (meta >> 16) & 15, nt = meta >> 20;
+          const int ks4 = (meta >> 16) & 15, nt = meta >> 21;
           const float* bi = img + (meta & 0xffff) + nt * ks4 * 256 + 16 * h;
           const bool two = NT > 1 && nt > 1;
 #pragma unroll
@@ -426,7 +461,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(Dee
         for (int l = 2; l < a.nl - a.last16; ++l) {
           const int meta = a.meta[l];
           const int ks4 = (meta >> 16) & 15;
-          const bool two = NT > 1 && (meta >> 20) > 1;
+          const bool two = NT > 1 && (meta >> 21) > 1;
           const float* A0 = img + (meta & 0xffff) + 4 * lane;
           const float* A1 = A0 + ks4 * 256;
 #pragma unroll
@@ -524,6 +559,151 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(Dee
           }
         }
         }
+      } else {
+        // One chain at a time (W = 128): user A's layers, then user B's (a rolled
+        // loop), each with NT tiles of accumulators for a layer's outputs and NT for its inputs
+        // (two chains of four tiles would need 256 registers for them); only the last layer's
+        // units of user A stay live across user B's chain.  The GMF terms of both halves go
+        // with user A's layer 2.
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        f32x16 c[NT], x[NT], xU[NT];  // xU: user A's last 32x32x2 layer (x: user B's at the end)
+        f32x4 d0 = z, d1 = z, dU0 = z, dU1 = z;  // last 16x16x4 layer: item blocks 0 / 1
+        float4 w[NT];
+#pragma unroll 1
+        for (int ch = 0; ch < 2; ++ch) {
+          {
+            const float* pC = &ps[(urA + ch) * W + h * (W / 2)];
+            const float* qh = qrow + h * (W / 2);
+            const int ks4 = (meta1 >> 16) & 31, nt = meta1 >> 21;
+            const float* A0 = img + (meta1 & 0xffff) + 4 * lane;
+            {  // group 0: the accumulators start from 0
+              const float4 q = *reinterpret_cast<const float4*>(qh);
+              const float4 pc = *reinterpret_cast<const float4*>(pC);
+              DM1_LOADW(0);
+              DM1_STEP(x, fmaxf(pc.x + q.x, 0.f), true);
+              DM1_STEP(y, fmaxf(pc.y + q.y, 0.f), false);
+              DM1_STEP(z, fmaxf(pc.z + q.z, 0.f), false);
+              DM1_STEP(w, fmaxf(pc.w + q.w, 0.f), false);
+              if (ch == 0) gmf8(0);
+            }
+            for (int s4 = 1; s4 < ks4; ++s4) {
+              const float4 q = *reinterpret_cast<const float4*>(qh + 4 * s4);
+              const float4 pc = *reinterpret_cast<const float4*>(pC + 4 * s4);
+              DM1_LOADW(s4);
+              DM1_STEP(x, fmaxf(pc.x + q.x, 0.f), false);
+              DM1_STEP(y, fmaxf(pc.y + q.y, 0.f), false);
+              DM1_STEP(z, fmaxf(pc.z + q.z, 0.f), false);
+              DM1_STEP(w, fmaxf(pc.w + q.w, 0.f), false);
+              if (ch == 0 && s4 < MFP / 8) gmf8(s4);
+            }
+            if (ch == 0)
+              for (int g = ks4; g < MFP / 8; ++g) gmf8(g);
+          }
+          auto epilogue = [&](int meta) {  // x = relu(acc + b): fmaxf(acc + b, 0), the chain's
+            const int ks4 = (meta >> 16) & 31, nt = meta >> 21;
+            const float* bi = img + (meta & 0xffff) + nt * ks4 * 256 + 16 * h;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+#pragma unroll
+              for (int t = 0; t < NT; ++t) {
+                const bool on = t == 0 || t < nt;
+                const float bt = on ? bi[32 * t + r] : 0.f;
+                x[t][r] = on ? fmaxf(c[t][r] + bt, 0.f) : 0.f;
+              }
+            }
+          };
+          epilogue(meta1);
+          // layers 3..: B operand of step s = 16t + r is x_t[r] (unit 2s + h), from registers
+          for (int l = 2; l < a.nl - a.last16; ++l) {
+            const int meta = a.meta[l];
+            const int ks4 = (meta >> 16) & 31, nt = meta >> 21;
+            const float* A0 = img + (meta & 0xffff) + 4 * lane;
+#pragma unroll
+            for (int s4 = 0; s4 < 4 * NT; ++s4) {
+              if (s4 < ks4) {
+                DM1_LOADW(s4);
+                const int r0 = (4 * s4) & 15;
+                const f32x16& v = x[s4 >> 2];
+                DM1_STEP(x, v[r0], s4 == 0);
+                DM1_STEP(y, v[r0 + 1], false);
+                DM1_STEP(z, v[r0 + 2], false);
+                DM1_STEP(w, v[r0 + 3], false);
+              }
+            }
+            epilogue(meta);
+          }
+          if (a.last16) {
+            // last layer (<= 16 outputs) on v_mfma_f32_16x16x4f32, as in the two-chain body:
+            // this user's two 16-item blocks
+            const int meta = a.meta[a.nl - 1];
+            const int g4 = (meta >> 16) & 31;
+            const float* A16 = img + (meta & 0xffff) + 4 * lane;
+            d0 = z;
+            d1 = z;
+            float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int st = 0; st < 8 * NT; ++st) {
+              if (st < 4 * g4) {
+                if ((st & 3) == 0) w4 = *reinterpret_cast<const float4*>(A16 + 256 * (st >> 2));
+                const float wv = (st & 3) == 0 ? w4.x : (st & 3) == 1 ? w4.y : (st & 3) == 2 ? w4.z : w4.w;
+                const int t = st >> 3, r = (2 * st) & 15;
+                const auto pa = __builtin_amdgcn_permlane32_swap(
+                    __float_as_uint(x[t][r]), __float_as_uint(x[t][r + 1]), false, false);
+                const auto qa = __builtin_amdgcn_permlane16_swap(pa[0], pa[1], false, false);
+                d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv, __uint_as_float(qa[0]), d0, 0, 0, 0);
+                d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv, __uint_as_float(qa[1]), d1, 0, 0, 0);
+              }
+            }
+          }
+          if (ch == 0) {
+            dU0 = d0;
+            dU1 = d1;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) xU[t] = x[t];
+          }
+        }
+        if (a.last16) {
+          // the 4 x 4 transpose of (block set, 16-lane row) that brings all 16 units of
+          // (user h, item l & 31) into lane l, then the chain's MLP terms
+          const int meta = a.meta[a.nl - 1];
+          const float* b16 = img + (meta & 0xffff) + ((meta >> 16) & 31) * 256;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const auto x02 = __builtin_amdgcn_permlane32_swap(
+                __float_as_uint(dU0[i]), __float_as_uint(d0[i]), false, false);
+            const auto x13 = __builtin_amdgcn_permlane32_swap(
+                __float_as_uint(dU1[i]), __float_as_uint(d1[i]), false, false);
+            const auto y01 = __builtin_amdgcn_permlane16_swap(x02[0], x13[0], false, false);
+            const auto y23 = __builtin_amdgcn_permlane16_swap(x02[1], x13[1], false, false);
+            dU0[i] = __uint_as_float(y01[0]);  // unit i
+            dU1[i] = __uint_as_float(y01[1]);  // unit 4 + i
+            d0[i] = __uint_as_float(y23[0]);  // unit 8 + i
+            d1[i] = __uint_as_float(y23[1]);  // unit 12 + i
+          }
+#pragma unroll
+          for (int u = 0; u < 16; ++u) {
+            if (u < a.dl) {
+              const float v = (u < 4 ? dU0 : u < 8 ? dU1 : u < 12 ? d0 : d1)[u & 3];
+              s = fmaf(wm[u], fmaxf(v + b16[u], 0.f), s);
+            }
+          }
+        } else {
+          // MLP terms of the chain: one permlane32 swap of (x_A, x_B) gives every lane of half
+          // 0 user A's even (r[0]) and odd (r[1]) units, and every lane of half 1 user B's
+#pragma unroll
+          for (int t = 0; t < NT; ++t) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int jj = 32 * t + 2 * r;
+              if (jj < a.dl) {
+                const auto sw = __builtin_amdgcn_permlane32_swap(
+                    __float_as_uint(xU[t][r]), __float_as_uint(x[t][r]), false, false);
+                s = fmaf(wm[jj], __uint_as_float(sw[0]), s);
+                s = fmaf(wm[jj + 1], __uint_as_float(sw[1]), s);  // wm zero past dl: exact
+              }
+            }
+          }
+        }
       }
       float score = s + bpv;
       const int64_t bM = h ? bB : bA;
@@ -563,6 +743,8 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void ncf_deep_mfma_kernel(Dee
     }
   }
 }
+#undef DM1_STEP
+#undef DM1_LOADW
 #undef DM_ACC
 #undef DM_STEP
 
@@ -584,18 +766,20 @@ static hnm_status deep_check(const hnm_ncf_deep_weights* w) {
   return HNM_OK;
 }
 
-// MFMA tile layout of a tower; false when it does not fit (widths > 64, mf > 128, an LDS
-// image beyond a CU's 160 KB)
+// MFMA tile layout of a tower; false when it does not fit (widths > 128, mf > 128, an LDS
+// image plus tiles beyond a CU's 160 KB, e.g. three 128 x 128 layers)
 struct DeepMLayout {
   DeepPack pk;
+  int w;       // P / Q row width: 64, or 128 when a layer is wider than 64
   int mfp;     // GMF width padded to 32, 64 or 128
-  int nt;      // max 32-unit tiles of an MFMA layer (1 or 2)
+  int nt;      // the instantiation's 32-unit tiles a layer: W = 64: 1 or 2, W = 128: 2 or 4
   size_t lds;  // dynamic LDS bytes
 };
 static bool deep_mfma_layout(const hnm_ctx* ctx, const hnm_ncf_deep_weights* w, DeepMLayout* o) {
   if (!ctx->deep_mfma || w->mf > 128 || w->num_items >= INT_BIG) return false;
   for (int l = 1; l <= w->nl; ++l)
-    if (w->dims[l] > 64) return false;
+    if (w->dims[l] > 128) return false;
+  o->w = w->dims[1] <= 64 ? 64 : 128;
   DeepPack& pk = o->pk;
   pk = DeepPack{};
   pk.nl = w->nl;
@@ -621,13 +805,15 @@ static bool deep_mfma_layout(const hnm_ctx* ctx, const hnm_ncf_deep_weights* w, 
     o->nt = std::max(o->nt, pk.nt[l]);
   }
   pk.img_n = off;
+  if (o->nt > 2) o->w = 128;  // a later layer wider than 64: the one-chain instantiations
+  o->nt = o->nt > 2 ? 4 : o->w == 128 ? 2 : o->nt;
   o->mfp = w->mf <= 32 ? 32 : w->mf <= 64 ? 64 : 128;
-  o->lds = (size_t)4 * (off + TILE * DM_QRS + TILE * (o->mfp + 4) + DM_NU * DM_W +
-                        DM_NU * o->mfp + o->mfp + 64);
+  o->lds = (size_t)4 * (off + TILE * (o->w + 4) + TILE * (o->mfp + 4) + DM_NU * o->w +
+                        DM_NU * o->mfp + o->mfp + dm_wpn(o->w, o->nt));
   return o->lds <= 160 * 1024 && off < 65536;
 }
 
-// Workspace: P [B, 64] and Q [I, 64] (pair-permuted, zero padded), the packed weight image,
+// Workspace: P [B, W] and Q [I, W] (pair-permuted, zero padded), the packed weight image,
 // the GMF item rows padded to mfp columns when the table is not already so, then `extra`
 // bytes for the caller.
 static hnm_status deep_mfma_tables(hnm_ctx* ctx, const hnm_ncf_deep_weights* w,
@@ -636,7 +822,8 @@ static hnm_status deep_mfma_tables(hnm_ctx* ctx, const hnm_ncf_deep_weights* w,
   const int64_t I = w->num_items;
   const int h = w->dims[0] / 2, d1 = w->dims[1];
   const bool gcopy = w->mf != lay.mfp || (uintptr_t)w->gmf_item % 16 != 0;
-  const size_t szP = hnm_align((size_t)B * DM_W * 4), szQ = hnm_align((size_t)I * DM_W * 4);
+  const int W = lay.w;
+  const size_t szP = hnm_align((size_t)B * W * 4), szQ = hnm_align((size_t)I * W * 4);
   const size_t szI = hnm_align((size_t)std::max(lay.pk.img_n, 4) * 4);
   const size_t szG = gcopy ? hnm_align((size_t)I * lay.mfp * 4) : 0;
   void* ws;
@@ -648,14 +835,14 @@ static hnm_status deep_mfma_tables(hnm_ctx* ctx, const hnm_ncf_deep_weights* w,
   float* img = (float*)cur; cur += szI;
   float* Gc = (float*)cur; cur += szG;
   *extra_out = cur;
-  if (d1 < DM_W) {
+  if (d1 < W) {
     HNM_HIP_CHECK(hipMemsetAsync(P, 0, szP + szQ, ctx->stream));
   }
   st = hnm_linear_rows_f32(ctx, w->mlp_user, h, ids, w->num_users, B, h, w->w[0], 2 * h,
-                           w->b[0], d1, P, DM_W, 1);
+                           w->b[0], d1, P, W, 1);
   if (st) return st;
   st = hnm_linear_rows_f32(ctx, w->mlp_item, h, nullptr, I, I, h, w->w[0] + h, 2 * h, nullptr,
-                           d1, Q, DM_W, 1);
+                           d1, Q, W, 1);
   if (st) return st;
   if (gcopy) {
     HNM_HIP_CHECK(hipMemsetAsync(Gc, 0, szG, ctx->stream));
@@ -687,41 +874,54 @@ static hnm_status deep_mfma_tables(hnm_ctx* ctx, const hnm_ncf_deep_weights* w,
   m.img_n = lay.pk.img_n;
   m.last16 = lay.pk.last16;
   for (int l = 1; l < w->nl; ++l)
-    m.meta[l] = lay.pk.aoff[l] | lay.pk.ks4[l] << 16 | lay.pk.nt[l] << 20;
+    m.meta[l] = lay.pk.aoff[l] | lay.pk.ks4[l] << 16 | lay.pk.nt[l] << 21;
   m.K = 1;
   m.err = ctx->err_dev;
   return HNM_OK;
 }
 
-template <int NT, int MFP, bool DENSE>
+// the item partitions of a call (the launch and the candidate buffers' size agree on them)
+static Partition deep_mfma_partition(const hnm_ctx* ctx, const DeepMLayout& lay, int64_t I,
+                                     int64_t B) {
+  return choose_partition(I, hnm_cdiv(B, DM_NU), ctx->num_cus, TILE, dm_occ(lay.w, lay.nt));
+}
+
+template <int W, int NT, int MFP, bool DENSE>
 static hnm_status deep_mfma_launch1(hnm_ctx* ctx, DeepMArgs a, const DeepMLayout& lay) {
   const int64_t ublocks = hnm_cdiv(a.B, DM_NU);
-  const Partition part = choose_partition(a.num_items, ublocks, ctx->num_cus, TILE, NT == 1 ? 3 : 2);
+  const Partition part = deep_mfma_partition(ctx, lay, a.num_items, a.B);
   a.ipp = part.ipp;
   a.NP = part.np;
   HNM_REQUIRE(ublocks < ((int64_t)1 << 31), HNM_EUNSUPPORTED, "ncf_deep: batch too large");
   if (lay.lds > 64 * 1024)  // e.g. two 64-wide MFMA layers: one workgroup a CU
-    (void)hipFuncSetAttribute((const void*)ncf_deep_mfma_kernel<NT, MFP, DENSE>,
+    (void)hipFuncSetAttribute((const void*)ncf_deep_mfma_kernel<W, NT, MFP, DENSE>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.lds);
   hnm_timer_begin(ctx, HNM_TIME_SCORE);
-  hipLaunchKernelGGL((ncf_deep_mfma_kernel<NT, MFP, DENSE>),
+  hipLaunchKernelGGL((ncf_deep_mfma_kernel<W, NT, MFP, DENSE>),
                      dim3((unsigned)ublocks, (unsigned)part.np), dim3(256), lay.lds, ctx->stream, a);
   hnm_timer_end(ctx, HNM_TIME_SCORE);
   HNM_LAUNCH_CHECK();
   return HNM_OK;
 }
 
-// NT = 1 when every MFMA layer has <= 32 outputs (one 32-unit tile: half the registers), else 2
+// W = 64: NT = 1 when every MFMA layer has <= 32 outputs (one 32-unit tile: half the registers),
+// else 2; W = 128 (a layer wider than 64): NT = 2 or 4
 template <bool DENSE>
 static hnm_status deep_mfma_launch(hnm_ctx* ctx, const DeepMArgs& a, const DeepMLayout& lay) {
-#define HNM_DEEP_MFP(NTV)                                                  \
-  return lay.mfp == 32   ? deep_mfma_launch1<NTV, 32, DENSE>(ctx, a, lay)  \
-         : lay.mfp == 64 ? deep_mfma_launch1<NTV, 64, DENSE>(ctx, a, lay)  \
-                         : deep_mfma_launch1<NTV, 128, DENSE>(ctx, a, lay);
-  if (lay.nt > 1) {
-    HNM_DEEP_MFP(2)
+#define HNM_DEEP_MFP(WV, NTV)                                                  \
+  return lay.mfp == 32   ? deep_mfma_launch1<WV, NTV, 32, DENSE>(ctx, a, lay)  \
+         : lay.mfp == 64 ? deep_mfma_launch1<WV, NTV, 64, DENSE>(ctx, a, lay)  \
+                         : deep_mfma_launch1<WV, NTV, 128, DENSE>(ctx, a, lay);
+  if (lay.w == 128) {
+    if (lay.nt > 2) {
+      HNM_DEEP_MFP(128, 4)
+    }
+    HNM_DEEP_MFP(128, 2)
   }
-  HNM_DEEP_MFP(1)
+  if (lay.nt > 1) {
+    HNM_DEEP_MFP(64, 2)
+  }
+  HNM_DEEP_MFP(64, 1)
 #undef HNM_DEEP_MFP
 }
 
@@ -850,7 +1050,7 @@ static hnm_status deep_topk_exact(hnm_ctx* ctx, const hnm_ncf_deep_weights* w,
   DeepMLayout lay;
   hnm_status st;
   if (deep_mfma_layout(ctx, w, &lay)) {
-    const Partition part = choose_partition(I, hnm_cdiv(B, DM_NU), ctx->num_cus, TILE, lay.nt == 1 ? 3 : 2);
+    const Partition part = deep_mfma_partition(ctx, lay, I, B);
     const size_t szC = hnm_align((size_t)B * part.np * K * 4);
     DeepMArgs m;
     void* extra;
@@ -865,7 +1065,8 @@ static hnm_status deep_topk_exact(hnm_ctx* ctx, const hnm_ncf_deep_weights* w,
     return hnm_topk_merge_i32(ctx, m.cv, m.ci, B, 1, 0, (int64_t)part.np * K, part.np * K, K, ov,
                               oi);
   }
-  // wide towers: dense rows of <= 256 MB per user chunk in the workspace + the row top-k
+  // towers wider than 128 (or past the LDS budget): dense rows of <= 256 MB per user chunk in
+  // the workspace + the row top-k
   const int64_t step = std::max<int64_t>(1, std::min<int64_t>(B, ((int64_t)1 << 26) / I));
   DeepArgs a;
   void* extra;
@@ -1003,5 +1204,14 @@ extern "C" hnm_status hnm_ncf_deep_topk_f32(hnm_ctx* ctx, const hnm_ncf_deep_wei
                          k, out_val ? out_val + b0 * k : nullptr, out_idx + b0 * k);
     if (st) return st;
   }
+  return HNM_OK;
+}
+
+extern "C" hnm_status hnm_ncf_deep_route(hnm_ctx* ctx, const hnm_ncf_deep_weights* w, int* route) {
+  hnm_status st = deep_check(w);
+  if (st) return st;
+  HNM_REQUIRE(ctx && route, HNM_EINVAL, "ncf_deep_route: NULL argument");
+  DeepMLayout lay;
+  *route = deep_mfma_layout(ctx, w, &lay) ? 1 : 0;
   return HNM_OK;
 }

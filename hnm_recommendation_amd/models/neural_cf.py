@@ -14,8 +14,8 @@ Linear -> ReLU per consecutive pair of mlp_dims, e.g. [64, 32] or [128, 64, 32, 
 exact fp32 deep-tower kernels: pair scores for forward and dense rows for predict_all_items
 (hnm_ncf_deep_scores_f32), and for recommend with k <= 64 the fused deep top-k
 (hnm_ncf_deep_topk_f32: f32-MFMA layer chains over item tiles with per-partition top-k lists for
-towers of widths <= 64, dense chunks + the row top-k inside the C entry for wider ones); k > 64
-takes dense rows + the row top-k kernel.
+towers of widths <= 128, dense chunks + the row top-k inside the C entry for wider ones); k > 64
+takes dense rows + the row top-k kernel.  `scoring_route()` tells which of them a tower takes.
 """
 from __future__ import annotations
 
@@ -127,6 +127,20 @@ class NeuralCF(RecModule):
             c, C.byref(w), _lib.ptr(u), B, _lib.ptr(items), _lib.ptr(out),
             out.stride(0) if items is None else 1), "hnm_ncf_deep_scores_f32")
         return out
+
+    def scoring_route(self) -> str:
+        """The kernels predict_all_items / recommend take for this tower on the module's
+        device: "fused" (the certified two-layer kernels, `_fused()`), "mfma" (the fp32-MFMA tile
+        kernel with fused partition top-k lists: widths <= 128 whose packed weights fit a CU's
+        LDS) or "per_pair" (the per-pair LDS kernel + dense-chunk row top-k: wider towers, or
+        HNM_OPT_DEEP_MFMA = 0).  hnm_ncf_deep_route: no launch, no sync."""
+        if self._fused():
+            return "fused"
+        w, keep = self._deep_weights()
+        route = C.c_int(-1)
+        _lib.check(_lib.fn("hnm_ncf_deep_route")(_lib.ctx(keep[0].device), C.byref(w),
+                                                 C.byref(route)), "hnm_ncf_deep_route")
+        return "mfma" if route.value == 1 else "per_pair"
 
     def _weights(self):
         """(hnm_ncf_weights, tensors it points into).  When every parameter already is a
@@ -263,7 +277,7 @@ class NeuralCF(RecModule):
 
     def _deep_topk(self, u, hu, k, mptr, midx):
         """Deep towers: hnm_ncf_deep_topk_f32 for k <= 64 (the fp32-MFMA scan with fused
-        per-partition top-k lists where the tower's widths are <= 64, else dense rows per user
+        per-partition top-k lists where the tower's widths are <= 128, else dense rows per user
         chunk in the library's workspace + the row top-k kernel); k > 64 (serve path, up to
         100): dense rows for a chunk of users (<= 256 MB of scores) + the row top-k kernel with
         the chunk's slice of the CSR mask (absolute offsets into mask_idx)."""

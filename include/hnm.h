@@ -89,9 +89,11 @@ enum { HNM_OPT_PREFILTER = 1,
                                   champion sample alone (the gate costs ~2 % of the init-weight
                                   step) */
        HNM_OPT_DEEP_MFMA = 5   /* deep NeuralCF towers (hnm_ncf_deep_*): 1 (default) = the
-                                  fp32-MFMA tile kernel where the tower fits it (widths <= 64,
-                                  mf <= 128); 0 = the per-pair LDS kernel everywhere (same
-                                  scores bitwise: the A/B and parity switch) */,
+                                  fp32-MFMA tile kernel where the tower fits it (widths <= 128,
+                                  mf <= 128, weight image + tiles within a CU's 160 KB of
+                                  LDS); 0 = the per-pair LDS kernel everywhere (same scores
+                                  bitwise: the A/B and parity switch).  hnm_ncf_deep_route
+                                  tells which one a tower takes */,
        HNM_OPT_LINEAR_MFMA = 6 /* hnm_linear_rows_f32 (every per-call layer-1 projection): 1
                                   (default) = the fp32-MFMA kernel where K % 32 == 0 (exact fp32
                                   fma chain in k order: bitwise the VALU kernel); 0 = the VALU
@@ -311,13 +313,18 @@ hnm_status hnm_ncf_deep_scores_f32(hnm_ctx* ctx, const hnm_ncf_deep_weights* w,
  * bound carried through |wp3|^T |W3| |W2|, exact fp32 re-scoring of the survivors by the deep
  * chain (outputs bitwise the exact path's); rows the bound cannot serve take the exact scan
  * (their count is read back: the call synchronizes its stream).  Otherwise towers with every
- * width dims[1..nl] <= 64 and mf <= 128 take the fp32-MFMA scan that keeps per-partition top-k
- * lists (no [B, I] score matrix); wider towers score dense rows per user chunk in the
- * workspace and take the row top-k kernel. */
+ * width dims[1..nl] <= 128 and mf <= 128 take the fp32-MFMA scan that keeps per-partition top-k
+ * lists (no [B, I] score matrix); wider towers (and towers whose packed weights do not fit a
+ * CU's LDS, e.g. three 128 x 128 layers) score dense rows per user chunk in the workspace and
+ * take the row top-k kernel. */
 hnm_status hnm_ncf_deep_topk_f32(hnm_ctx* ctx, const hnm_ncf_deep_weights* w,
                                  const int64_t* user_ids, int64_t B, const int64_t* mask_ptr,
                                  const int32_t* mask_idx, int k, float* out_val,
                                  int64_t* out_idx);
+/* Which exact-path kernel hnm_ncf_deep_scores_f32 (dense) / hnm_ncf_deep_topk_f32 take for this
+ * tower on this ctx: 0 = per-pair LDS kernel (+ dense-chunk row top-k), 1 = fp32-MFMA tile kernel
+ * (+ fused partition lists).  Honours HNM_OPT_DEEP_MFMA.  No launch, no sync. */
+hnm_status hnm_ncf_deep_route(hnm_ctx* ctx, const hnm_ncf_deep_weights* w, int* route);
 /* Diagnostics of that pre-filter (no reference counterpart): approx[b, i] = the f16 scan's score
  * of item i without bp, bound[b, i] its certified bound ([B, lda], real units); |approx + bp -
  * exact| <= bound for every pair (tests check it on the full catalogue). */

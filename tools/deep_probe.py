@@ -21,7 +21,8 @@ STEPS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 DEV = torch.device("cuda", 0)
 torch.cuda.set_device(0)
 U, I = syn.HM_USERS, syn.HM_ITEMS
-for mf, dims in [(64, (128, 64, 32, 16)), (32, (64, 32, 16, 8)), (64, (128, 64, 64, 32))]:
+for mf, dims in [(64, (128, 64, 32, 16)), (32, (64, 32, 16, 8)), (64, (128, 64, 64, 32)),
+                 (64, (256, 128, 64)), (64, (256, 128, 128, 16))]:
     sd = syn.ncf_state_dict(U, I, mf, dims, seed=3, bias_scale=0.05)
     m = NeuralCF(U, I, mf_dim=mf, mlp_dims=list(dims))
     m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
