@@ -16,8 +16,8 @@ CSRC = os.path.join(PKG, "csrc")
 BUILD = os.path.join(REPO, "build", "obj")
 LIB = os.path.join(PKG, "libhnm_mi355x.so")
 SOURCES = ["api.hip", "score.hip", "dot_cert.hip", "ncf.hip", "ncf_cert.hip", "ncf_deep.hip", "graph.hip",
-           "widedeep.hip", "eval.hip", "topk_sort.hip", "collective.hip"]
-HEADERS = ["hnm_device.h", "hnm_internal.h", "dot_internal.h", "ncf_internal.h", "sample_kth.h"]
+           "widedeep.hip", "widedeep_cert.hip", "widedeep_rescore.hip", "eval.hip", "topk_sort.hip",
+           "collective.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
@@ -28,8 +28,9 @@ def _mtime(p):
 
 
 def _deps_mtime():
-    paths = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(REPO, "include", "hnm.h")]
-    return max(_mtime(p) for p in paths)
+    # every header in csrc/ (each unit depends on all of them) and the public one
+    paths = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
+    return max(_mtime(p) for p in paths + [os.path.join(REPO, "include", "hnm.h")])
 
 
 def _compile(src):

@@ -201,6 +201,10 @@ hnm_status hnm_topk_merge_rows(hnm_ctx* ctx, const float* cv, const int32_t* ci,
                                int64_t G, int64_t gstride, int64_t bstride, int kc, int k,
                                float* ov, int64_t* oi, const int32_t* rows,
                                const int32_t* nrows, int64_t dyn_items = 0, int dyn_cus = 0);
+// the same for batch rows 0 .. B
+hnm_status hnm_topk_merge_i32(hnm_ctx* ctx, const float* cv, const int32_t* ci, int64_t B,
+                              int64_t G, int64_t gstride, int64_t bstride, int kc, int k,
+                              float* ov, int64_t* oi);
 
 // p[0, n) = v on the ctx stream
 hnm_status hnm_fill_f32(hnm_ctx* ctx, float* p, int64_t n, float v);

@@ -23,10 +23,6 @@
 #include "hnm_device.h"
 #include "ncf_internal.h"
 
-hnm_status hnm_topk_merge_i32(hnm_ctx* ctx, const float* cv, const int32_t* ci, int64_t B,
-                              int64_t G, int64_t gstride, int64_t bstride, int kc, int k,
-                              float* ov, int64_t* oi);
-
 // ------------------------------------------------------------------ 32-user kernel
 template <bool DENSE>
 __global__ __launch_bounds__(256, 2) void ncf32_kernel(

@@ -21,10 +21,6 @@
 #include "hnm_internal.h"
 #include "ncf_internal.h"
 
-hnm_status hnm_topk_merge_i32(hnm_ctx* ctx, const float* cv, const int32_t* ci, int64_t B,
-                              int64_t G, int64_t gstride, int64_t bstride, int kc, int k,
-                              float* ov, int64_t* oi);
-
 struct DeepArgs {
   const float* P;        // [B, d1]   user halves of layer 1 (+ b1)
   const float* Q;        // [nq, d1]  item halves (all items, or the pairs' items)

@@ -25,11 +25,6 @@
 #include "dot_internal.h"
 #include "sample_kth.h"
 
-hnm_status hnm_topk_merge_i32(hnm_ctx* ctx, const float* cv, const int32_t* ci, int64_t B,
-                              int64_t G, int64_t gstride, int64_t bstride, int kc, int k,
-                              float* ov, int64_t* oi);
-
-
 // ------------------------------------------------------------------ dot kernel
 // LIST keeps 32 user lists in registers (2 workgroups/CU); the list-free d<=64 modes run 4 (measured faster than 3 despite a small spill).
 template <int DP, int MODE, bool BIAS>

@@ -207,13 +207,21 @@ def test_lightning_checkpoint_fixture_loads_like_serve_py():
     assert srv.models["lightgcn"].embedding_dim == 16
 
 
-def test_build_tracks_every_csrc_header():
+def test_build_tracks_every_csrc_header(tmp_path, monkeypatch):
     """Incremental builds rebuild every object when any csrc header changes (a header left
-    out of build.HEADERS once left stale objects calling an old signature)."""
+    out of a hand-kept list once left stale objects calling an old signature): the dependency
+    time follows every *.h present in csrc/, a header nobody registered included."""
     import glob
     from hnm_recommendation_amd import build
-    hdrs = {os.path.basename(p) for p in glob.glob(os.path.join(build.CSRC, "*.h"))}
-    assert hdrs <= set(build.HEADERS), sorted(hdrs - set(build.HEADERS))
+    hdrs = glob.glob(os.path.join(build.CSRC, "*.h"))
+    assert len(hdrs) >= 6
+    assert build._deps_mtime() >= max(os.path.getmtime(p) for p in hdrs)
+    new = tmp_path / "brand_new.h"
+    new.write_text("// added after the last build\n")
+    later = build._deps_mtime() + 1000.0
+    os.utime(new, (later, later))
+    monkeypatch.setattr(build, "CSRC", str(tmp_path))
+    assert build._deps_mtime() == later
 
 
 def test_ncf_shard_scorer_dispatch():

@@ -1,4 +1,4 @@
-"""GPU: the certified f16 pre-filters (ncf_cert.hip, dot_cert.hip, widedeep.hip) under weight
+"""GPU: the certified f16 pre-filters (ncf_cert.hip, dot_cert.hip, widedeep_cert.hip) under weight
 distributions unlike the synthetic init -- what trained models look like, not what the
 generator draws (VERDICT r3 "Weak #6").
 

@@ -287,7 +287,7 @@ def wd_refine_debug(m, users, feats=None):
 
 @pytest.mark.parametrize("kw", [{}, {"bias_scale": 0.05, "randomize_bn": True, "emb_scale": 10.0}])
 def test_wd_refine_bound_holds_full_catalogue(kw):
-    """The cascade's refined bound (widedeep.hip wdc_refine_kernel, round 5): |approx - exact|
+    """The cascade's refined bound (widedeep_rescore.hip wdc_refine_kernel, round 5): |approx - exact|
     <= bound for every pair of 16 users x the H&M catalogue, and much tighter than the scan's."""
     m, _ = wd_model(20000, syn.HM_ITEMS, seed=1, **kw)
     users = torch.from_numpy(syn.user_batch(20000, 16, seed=5)).to(DEV)

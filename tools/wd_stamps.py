@@ -1,6 +1,6 @@
 """Per-phase cycle split of the W&D certified scan (diagnostic build only).
 
-    bash tools/build_variant.sh wdst hnm_recommendation_amd/csrc/widedeep.hip -DWD_STAMPS=1
+    bash tools/build_variant.sh wdst hnm_recommendation_amd/csrc/widedeep_cert.hip -DWD_STAMPS=1
     HNM_LIB_PATH=$PWD/tools/bin/libhnm_wdst.so python tools/wd_stamps.py
 
 Runs the bench's W&D step (configs[3]: 4,096 users x 105,542 items) twice and reads the
