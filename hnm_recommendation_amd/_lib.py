@@ -141,6 +141,18 @@ _SIGS = {
                                                 _i64, _p]),
     "hnm_widedeep_refine_debug_f32": (_i32, [_p, C.POINTER(WideDeepWeights), _p, _i64, _p, _p,
                                                 _i64, _p]),
+    # the catalogue entries with an item-feature table: ..., itf, item_features, ldf
+    "hnm_widedeep_topk_ex_f32": (_i32, [_p, C.POINTER(WideDeepWeights), _p, _i64, _p, _p, _p,
+                                        C.c_int, _p, _p, C.POINTER(WideDeepItemFeatures), _p,
+                                        _i64]),
+    "hnm_widedeep_scores_ex_f32": (_i32, [_p, C.POINTER(WideDeepWeights), _p, _i64, _p, _p, _i64,
+                                          C.POINTER(WideDeepItemFeatures), _p, _i64]),
+    "hnm_widedeep_prefilter_debug_ex_f32": (_i32, [_p, C.POINTER(WideDeepWeights), _p, _i64, _p,
+                                                   _p, _i64, _p,
+                                                   C.POINTER(WideDeepItemFeatures), _p, _i64]),
+    "hnm_widedeep_refine_debug_ex_f32": (_i32, [_p, C.POINTER(WideDeepWeights), _p, _i64, _p, _p,
+                                                _i64, _p, C.POINTER(WideDeepItemFeatures), _p,
+                                                _i64]),
     "hnm_mask_gather_csr": (_i32, [_p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p]),
     "hnm_rank_metrics_f64": (_i32, [_p, _p, _i64, _i64, _p, C.c_int, _p, _p, _i64, _p, _p, _p,
                                     _p, _p]),

@@ -15,6 +15,8 @@
 //            operand: k-step (rb, r) pairs row (r&3)+8(r>>2) of half 0 with +4 of half 1,
 //            and W3' is pre-permuted to the same k order, so no LDS round trip.
 //   final:   relu(D3 + b3') . w_d' (16-register epilogue + one cross-half shuffle)
+// Item features (the _ex entries) are per item: their layer-1 part is added to Q_i and their wide
+// cross to the per-item wide term before any of this runs (widedeep_features.hip).
 // Layer-2 row blocks are processed 4 at a time (64 accumulator registers) and fed into
 // the layer-3 accumulators (64 registers) as they complete.
 // (The certified split-f16 scan: widedeep_cert.hip; its re-scoring cascade: widedeep_rescore.hip.)
@@ -280,7 +282,7 @@ __global__ __launch_bounds__(256) void widedeep_pair_kernel(
 }
 
 // ------------------------------------------------------------------ host side
-static hnm_status wd_check(const hnm_widedeep_weights* w) {
+static hnm_status wd_check(const hnm_widedeep_weights* w, const WdItemFeat& F) {
   HNM_REQUIRE(w && w->deep_user && w->deep_item && w->w1 && w->b1 && w->w2 && w->b2 &&
                   w->wide_user && w->wide_item && w->final_deep && w->final_b && w->bn1_w &&
                   w->bn2_w,
@@ -292,6 +294,21 @@ static hnm_status wd_check(const hnm_widedeep_weights* w) {
               HNM_EUNSUPPORTED,
               "widedeep: the fused kernel covers 2- or 3-layer towers with widths <= "
               "512/256/128 (got %d/%d/%d)", w->l1, w->l2, w->l3);
+  if (F.on()) {
+    const hnm_widedeep_item_features* itf = F.itf;
+    HNM_REQUIRE(w->l1_in == (2 + (w->num_user_features > 0 ? 1 : 0) + 1) * w->d, HNM_EUNSUPPORTED,
+                "widedeep: deep input must be [e_u; e_i(; user features); item features] "
+                "(layer-1 input %d, embedding_dim %d)", w->l1_in, w->d);
+    HNM_REQUIRE(F.f && itf->dif_w && itf->dif_b, HNM_EINVAL,
+                "widedeep: item_features required (num_item_features > 0)");
+    HNM_REQUIRE(F.ldf >= itf->num_item_features, HNM_EINVAL,
+                "widedeep: item_features leading dimension %lld < %d", (long long)F.ldf,
+                itf->num_item_features);
+    HNM_REQUIRE(w->d <= WDF_MAX_D && itf->num_item_features <= WDF_MAX_F, HNM_EUNSUPPORTED,
+                "widedeep: the item-feature fold covers embedding_dim <= %d and <= %d item "
+                "features (got %d, %d)", WDF_MAX_D, WDF_MAX_F, w->d, itf->num_item_features);
+    return HNM_OK;
+  }
   HNM_REQUIRE(w->l1_in == 2 * w->d + (w->num_user_features > 0 ? w->d : 0), HNM_EUNSUPPORTED,
               "widedeep: deep input must be [e_u; e_i(; user features)] (item features are "
               "not available to predict_all_items, wide_deep.py:275)");
@@ -305,8 +322,8 @@ static int pow2_blocks(int width) {
   return p;
 }
 
-hnm_status wd_shape(const hnm_widedeep_weights* w, WdPrep* pr) {
-  hnm_status st = wd_check(w);
+hnm_status wd_shape(const hnm_widedeep_weights* w, WdPrep* pr, const WdItemFeat& F) {
+  hnm_status st = wd_check(w, F);
   if (st) return st;
   pr->K1P = (w->l1 + 7) / 8 * 8;
   pr->RB2 = pow2_blocks(w->l2);
@@ -334,7 +351,7 @@ static size_t wd_list_bytes(const hnm_ctx* ctx, int64_t n, int64_t I, int K) {
 }
 
 hnm_status wd_setup(hnm_ctx* ctx, const hnm_widedeep_weights* w, const int64_t* ids, int64_t B,
-                    const float* ufeat, size_t extra, WdSetup* S) {
+                    const float* ufeat, size_t extra, WdSetup* S, const WdItemFeat& F) {
   const int64_t I = w->num_items;
   WdPrep& pr = S->pr;
   const int K1P = pr.K1P;
@@ -350,9 +367,12 @@ hnm_status wd_setup(hnm_ctx* ctx, const hnm_widedeep_weights* w, const int64_t* 
   const size_t szF = ufeat ? hnm_align((size_t)B * w->num_user_features * 4) : 0;
   const size_t szU = hnm_align((size_t)B * 4);
   const size_t szT = w->num_user_features > 0 ? hnm_align((size_t)B * K1P * 4) : 0;
+  // the folded wide item term (item features with a wide cross); else w->wide_item as it is
+  const bool fold_wide = F.on() && F.itf->wif_w && F.itf->wide_feat;
+  const size_t szI = fold_wide ? hnm_align((size_t)I * 4) : 0;
   void* wsp;
   hnm_status st = hnm_workspace(ctx, szW2 + szW3 + szb2 + szb3 + szwd + 256 + szP + szQ + szX +
-                                         szF + szU + szT + hnm_align(extra), &wsp);
+                                         szF + szU + szT + szI + hnm_align(extra), &wsp);
   if (st) return st;
   char* q = (char*)wsp;
   pr.W2f = (float4*)q; q += szW2;
@@ -367,6 +387,8 @@ hnm_status wd_setup(hnm_ctx* ctx, const hnm_widedeep_weights* w, const int64_t* 
   float* WFu = (float*)q; q += szF;
   float* cu = (float*)q; q += szU;
   float* Tf = (float*)q; q += szT;
+  float* wIf = (float*)q; q += szI;
+  S->wI = fold_wide ? wIf : w->wide_item;
   S->Pu = Pu;
   S->Qi = Qi;
   S->cu = cu;
@@ -389,6 +411,10 @@ hnm_status wd_setup(hnm_ctx* ctx, const hnm_widedeep_weights* w, const int64_t* 
   st = hnm_linear_rows_f32(ctx, w->deep_item, w->d, nullptr, I, I, w->d, w->w1 + w->d, w->l1_in,
                            nullptr, w->l1, Qi, K1P, 1);
   if (st) return st;
+  if (F.on()) {
+    st = wd_fold_item_features(ctx, w, F, K1P, Qi, fold_wide ? wIf : nullptr);
+    if (st) return st;
+  }
   const float* wuf = nullptr;
   if (w->num_user_features > 0) {
     HNM_REQUIRE(ufeat && w->duf_w && w->duf_b, HNM_EINVAL,
@@ -437,7 +463,7 @@ hnm_status wd_exact(hnm_ctx* ctx, const hnm_widedeep_weights* w, const WdSetup& 
   if (timed) hnm_timer_begin(ctx, HNM_TIME_SCORE);
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, S.Pu, S.Qi, K1P, pr.W2f, pr.W3f,
-                       pr.b2p, pr.b3p, pr.wdp, S.cu, w->wide_item, n, I, ipp, mptr, midx, K, cv, ci,
+                       pr.b2p, pr.b3p, pr.wdp, S.cu, S.wI, n, I, ipp, mptr, midx, K, cv, ci,
                        (int)np, dense, ldo, rows);
   };
   const bool found = wd_dispatch<false>(pr.RB2, pr.OB, [&](auto R, auto O) {
@@ -451,29 +477,35 @@ hnm_status wd_exact(hnm_ctx* ctx, const hnm_widedeep_weights* w, const WdSetup& 
   return hnm_topk_merge_i32(ctx, cv, ci, n, 1, 0, np * K, (int)(np * K), K, ov, oi);
 }
 
-extern "C" hnm_status hnm_widedeep_topk_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
-                                            const int64_t* user_ids, int64_t B,
-                                            const float* user_features, const int64_t* mask_ptr,
-                                            const int32_t* mask_idx, int k, float* out_val,
-                                            int64_t* out_idx) {
+extern "C" hnm_status hnm_widedeep_topk_ex_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
+                                               const int64_t* user_ids, int64_t B,
+                                               const float* user_features,
+                                               const int64_t* mask_ptr, const int32_t* mask_idx,
+                                               int k, float* out_val, int64_t* out_idx,
+                                               const hnm_widedeep_item_features* itf,
+                                               const float* item_features, int64_t ldf) {
   HNM_CTX_DEVICE(ctx);
+  WdItemFeat F;
+  F.itf = itf;
+  F.f = item_features;
+  F.ldf = ldf;
   HNM_REQUIRE(k >= 1 && k <= 64 && (out_idx || B == 0), HNM_EINVAL, "widedeep_topk: fused path needs 1 <= k <= 64");
   HNM_REQUIRE(ctx && (user_ids || B == 0), HNM_EINVAL, "widedeep: NULL argument");
   WdSetup S;
-  hnm_status st = wd_shape(w, &S.pr);
+  hnm_status st = wd_shape(w, &S.pr, F);
   if (st) return st;
   if (B <= 0) return HNM_OK;
   const int64_t I = w->num_items;
   if (wdc_eligible(ctx, S.pr, I, k, false)) {
     const size_t extra = wdc_carve(ctx, S.pr, B, I, k, nullptr, nullptr);
-    st = wd_setup(ctx, w, user_ids, B, user_features, extra, &S);
+    st = wd_setup(ctx, w, user_ids, B, user_features, extra, &S, F);
     if (st) return st;
     WdcWs c;
     wdc_carve(ctx, S.pr, B, I, k, S.extra, &c);
     return wdc_topk(ctx, w, S, B, mask_ptr, mask_idx, k, c, out_val, out_idx);
   }
   const size_t lb = wd_list_bytes(ctx, B, I, k);
-  st = wd_setup(ctx, w, user_ids, B, user_features, lb, &S);
+  st = wd_setup(ctx, w, user_ids, B, user_features, lb, &S, F);
   if (st) return st;
   int64_t np, ipp;
   wd_partition(ctx, B, I, &np, &ipp);
@@ -483,21 +515,44 @@ extern "C" hnm_status hnm_widedeep_topk_f32(hnm_ctx* ctx, const hnm_widedeep_wei
                   nullptr, 0, true);
 }
 
+extern "C" hnm_status hnm_widedeep_topk_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
+                                            const int64_t* user_ids, int64_t B,
+                                            const float* user_features, const int64_t* mask_ptr,
+                                            const int32_t* mask_idx, int k, float* out_val,
+                                            int64_t* out_idx) {
+  return hnm_widedeep_topk_ex_f32(ctx, w, user_ids, B, user_features, mask_ptr, mask_idx, k,
+                                  out_val, out_idx, nullptr, nullptr, 0);
+}
+
+extern "C" hnm_status hnm_widedeep_scores_ex_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
+                                                 const int64_t* user_ids, int64_t B,
+                                                 const float* user_features, float* out,
+                                                 int64_t ldo,
+                                                 const hnm_widedeep_item_features* itf,
+                                                 const float* item_features, int64_t ldf) {
+  HNM_CTX_DEVICE(ctx);
+  WdItemFeat F;
+  F.itf = itf;
+  F.f = item_features;
+  F.ldf = ldf;
+  HNM_REQUIRE((out || B == 0) && w && ldo >= w->num_items, HNM_EINVAL, "widedeep_scores: bad output");
+  HNM_REQUIRE(ctx && (user_ids || B == 0), HNM_EINVAL, "widedeep: NULL argument");
+  WdSetup S;
+  hnm_status st = wd_shape(w, &S.pr, F);
+  if (st) return st;
+  if (B <= 0) return HNM_OK;
+  st = wd_setup(ctx, w, user_ids, B, user_features, 0, &S, F);
+  if (st) return st;
+  return wd_exact(ctx, w, S, B, nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr,
+                  nullptr, out, ldo, true);
+}
+
 extern "C" hnm_status hnm_widedeep_scores_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
                                               const int64_t* user_ids, int64_t B,
                                               const float* user_features, float* out,
                                               int64_t ldo) {
-  HNM_CTX_DEVICE(ctx);
-  HNM_REQUIRE((out || B == 0) && w && ldo >= w->num_items, HNM_EINVAL, "widedeep_scores: bad output");
-  HNM_REQUIRE(ctx && (user_ids || B == 0), HNM_EINVAL, "widedeep: NULL argument");
-  WdSetup S;
-  hnm_status st = wd_shape(w, &S.pr);
-  if (st) return st;
-  if (B <= 0) return HNM_OK;
-  st = wd_setup(ctx, w, user_ids, B, user_features, 0, &S);
-  if (st) return st;
-  return wd_exact(ctx, w, S, B, nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr,
-                  nullptr, out, ldo, true);
+  return hnm_widedeep_scores_ex_f32(ctx, w, user_ids, B, user_features, out, ldo, nullptr,
+                                    nullptr, 0);
 }
 
 extern "C" hnm_status hnm_widedeep_pair_scores_ex_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,

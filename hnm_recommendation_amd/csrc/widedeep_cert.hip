@@ -132,12 +132,6 @@ __device__ __forceinline__ void wd_split_relu2(wf2 z, wh2& hi, unsigned& alo) {
   alo = d & 0x7fff7fffu;
 }
 
-// pair-permuted position t of a layer-1 row -> layer-1 unit (hnm_linear_rows_f32 layout)
-__device__ __forceinline__ int wd_korig(int t, int K1P) {
-  const int half = K1P >> 1;
-  return t < half ? 2 * t : 2 * (t - half) + 1;
-}
-
 __device__ __forceinline__ float wd_pow2_below_inv(float m) {  // largest 2^e with m 2^e <= 1
   int e;
   (void)frexpf(m, &e);
@@ -1096,7 +1090,7 @@ hnm_status wdc_scan(hnm_ctx* ctx, const hnm_widedeep_weights* w, const WdSetup& 
   a.b3p = pr.b3p;
   a.wdp = pr.wdp;
   a.cu = S.cu;
-  a.wI = w->wide_item;
+  a.wI = S.wI;
   a.prm = c.prm;
   a.B = B;
   a.I = w->num_items;
@@ -1134,28 +1128,40 @@ hnm_status wdc_scan(hnm_ctx* ctx, const hnm_widedeep_weights* w, const WdSetup& 
   return HNM_OK;
 }
 
-extern "C" hnm_status hnm_widedeep_prefilter_debug_f32(hnm_ctx* ctx,
-                                                       const hnm_widedeep_weights* w,
-                                                       const int64_t* user_ids, int64_t B,
-                                                       const float* user_features,
-                                                       float* approx, int64_t lda,
-                                                       float* bound) {
+extern "C" hnm_status hnm_widedeep_prefilter_debug_ex_f32(
+    hnm_ctx* ctx, const hnm_widedeep_weights* w, const int64_t* user_ids, int64_t B,
+    const float* user_features, float* approx, int64_t lda, float* bound,
+    const hnm_widedeep_item_features* itf, const float* item_features, int64_t ldf) {
   HNM_CTX_DEVICE(ctx);
   HNM_REQUIRE(ctx && user_ids && approx && bound && w && lda >= w->num_items, HNM_EINVAL,
               "widedeep_prefilter_debug: bad argument");
+  WdItemFeat F;
+  F.itf = itf;
+  F.f = item_features;
+  F.ldf = ldf;
   WdSetup S;
-  hnm_status st = wd_shape(w, &S.pr);
+  hnm_status st = wd_shape(w, &S.pr, F);
   if (st) return st;
   HNM_REQUIRE(wdc_eligible(ctx, S.pr, w->num_items, 1, true), HNM_EUNSUPPORTED,
               "widedeep_prefilter_debug: tower shape not covered by the certified scan");
   if (B <= 0) return HNM_OK;
   const int64_t I = w->num_items;
   const size_t extra = wdc_carve(ctx, S.pr, B, I, 1, nullptr, nullptr);
-  st = wd_setup(ctx, w, user_ids, B, user_features, extra, &S);
+  st = wd_setup(ctx, w, user_ids, B, user_features, extra, &S, F);
   if (st) return st;
   WdcWs c;
   wdc_carve(ctx, S.pr, B, I, 1, S.extra, &c);
   st = wdc_prepare(ctx, w, S, B, c);
   if (st) return st;
   return wdc_scan(ctx, w, S, B, nullptr, nullptr, 1, c, WDC_DEBUG, approx, bound, lda);
+}
+
+extern "C" hnm_status hnm_widedeep_prefilter_debug_f32(hnm_ctx* ctx,
+                                                       const hnm_widedeep_weights* w,
+                                                       const int64_t* user_ids, int64_t B,
+                                                       const float* user_features,
+                                                       float* approx, int64_t lda,
+                                                       float* bound) {
+  return hnm_widedeep_prefilter_debug_ex_f32(ctx, w, user_ids, B, user_features, approx, lda,
+                                             bound, nullptr, nullptr, 0);
 }

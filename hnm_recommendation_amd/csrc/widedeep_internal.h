@@ -29,7 +29,17 @@ struct WdSetup {
   float* Pu;
   float* Qi;
   float* cu;
+  const float* wI;  // [I] per-item wide term: w->wide_item, or the item-feature fold's output
   char* extra;
+};
+
+// The item-feature table of an _ex call: weights, [I, Fi] features (row stride ldf).  on():
+// the call has item features (itf == NULL or Fi == 0: the plain entries' behaviour).
+struct WdItemFeat {
+  const hnm_widedeep_item_features* itf = nullptr;
+  const float* f = nullptr;
+  int64_t ldf = 0;
+  bool on() const { return itf && itf->num_item_features > 0; }
 };
 
 __device__ __forceinline__ float bn_a(const float* g, const float* v, int i, float eps) {
@@ -143,6 +153,12 @@ __device__ __forceinline__ float wd_tile_fp32(const float* __restrict__ prow,
     }
   }
   return fin;
+}
+
+// pair-permuted position t of a layer-1 row -> layer-1 unit (hnm_linear_rows_f32 layout)
+__device__ __forceinline__ int wd_korig(int t, int K1P) {
+  const int half = K1P >> 1;
+  return t < half ? 2 * t : 2 * (t - half) + 1;
 }
 
 // ------------------------------------------------------------------ instantiated tower shapes
@@ -336,10 +352,11 @@ struct WdcWs {
 
 // ------------------------------------------------------------------ widedeep.hip
 // validates the weights, fills pr's K1P / RB2 / OB; HNM_EUNSUPPORTED: shape not in WD_SHAPES
-hnm_status wd_shape(const hnm_widedeep_weights* w, WdPrep* pr);
-// Per-call preparation (see WdSetup); S->pr holds wd_shape's result.
+hnm_status wd_shape(const hnm_widedeep_weights* w, WdPrep* pr, const WdItemFeat& itf = {});
+// Per-call preparation (see WdSetup); S->pr holds wd_shape's result.  With item features the
+// fold kernel adds their layer-1 part to Q and writes the wide term wI (wd_fold_item_features).
 hnm_status wd_setup(hnm_ctx* ctx, const hnm_widedeep_weights* w, const int64_t* ids, int64_t B,
-                    const float* ufeat, size_t extra, WdSetup* S);
+                    const float* ufeat, size_t extra, WdSetup* S, const WdItemFeat& itf = {});
 // item partitions for blocks of upb users: about two workgroups per CU, >= 4 tiles each
 void wd_partition(const hnm_ctx* ctx, int64_t B, int64_t I, int64_t* np, int64_t* ipp,
                   int upb = 4);
@@ -351,6 +368,14 @@ hnm_status wd_exact(hnm_ctx* ctx, const hnm_widedeep_weights* w, const WdSetup& 
                     const int64_t* mptr, const int32_t* midx, int K, const int32_t* rows,
                     float* cv, int32_t* ci, float* ov, int64_t* oi, float* dense, int64_t ldo,
                     bool timed);
+
+// ------------------------------------------------------------------ widedeep_features.hip
+#define WDF_MAX_D 256  // embedding width and feature count the fold's LDS staging covers
+#define WDF_MAX_F 256
+// Q_i += W1[:, c:c+d] (dif_w f_i + dif_b) in place (pair-permuted, row stride K1P) and, with a
+// wide item-feature term, wI_i = wide_item[i] + wide_feat . (wif_w f_i + wif_b)
+hnm_status wd_fold_item_features(hnm_ctx* ctx, const hnm_widedeep_weights* w,
+                                 const WdItemFeat& itf, int K1P, float* Qi, float* wI);
 
 // ------------------------------------------------------------------ widedeep_cert.hip
 bool wdc_eligible(const hnm_ctx* ctx, const WdPrep& pr, int64_t I, int K, bool debug);

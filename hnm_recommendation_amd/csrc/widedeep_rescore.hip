@@ -560,7 +560,7 @@ static WdRescoreArgs wdc_rescore_args(const hnm_widedeep_weights* w, const WdSet
   r.b3p = S.pr.b3p;
   r.wdp = S.pr.wdp;
   r.cu = S.cu;
-  r.wI = w->wide_item;
+  r.wI = S.wI;
   r.prm = c.prm;
   r.B = B;
   r.W2hl = c.W2hl;
@@ -631,15 +631,19 @@ __global__ void wdc_debug_rows_kernel(int32_t* __restrict__ segi, int* __restric
   if (e < B) ns[e] = (int)I;
 }
 
-extern "C" hnm_status hnm_widedeep_refine_debug_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
-                                                    const int64_t* user_ids, int64_t B,
-                                                    const float* user_features, float* approx,
-                                                    int64_t lda, float* bound) {
+extern "C" hnm_status hnm_widedeep_refine_debug_ex_f32(
+    hnm_ctx* ctx, const hnm_widedeep_weights* w, const int64_t* user_ids, int64_t B,
+    const float* user_features, float* approx, int64_t lda, float* bound,
+    const hnm_widedeep_item_features* itf, const float* item_features, int64_t ldf) {
   HNM_CTX_DEVICE(ctx);
   HNM_REQUIRE(ctx && user_ids && approx && bound && w && lda >= w->num_items, HNM_EINVAL,
               "widedeep_refine_debug: bad argument");
+  WdItemFeat F;
+  F.itf = itf;
+  F.f = item_features;
+  F.ldf = ldf;
   WdSetup S;
-  hnm_status st = wd_shape(w, &S.pr);
+  hnm_status st = wd_shape(w, &S.pr, F);
   if (st) return st;
   HNM_REQUIRE(wdc_eligible(ctx, S.pr, w->num_items, 1, true), HNM_EUNSUPPORTED,
               "widedeep_refine_debug: tower shape not covered by the certified scan");
@@ -648,7 +652,7 @@ extern "C" hnm_status hnm_widedeep_refine_debug_f32(hnm_ctx* ctx, const hnm_wide
   HNM_REQUIRE(B * I < ((int64_t)1 << 31), HNM_EINVAL, "widedeep_refine_debug: B * I >= 2^31");
   const size_t cb = wdc_carve(ctx, S.pr, B, I, 1, nullptr, nullptr);
   const size_t lb = hnm_align((size_t)B * I * 4) + hnm_align((size_t)B * 4) + hnm_align((size_t)(B + 1) * 4);
-  st = wd_setup(ctx, w, user_ids, B, user_features, cb + lb, &S);
+  st = wd_setup(ctx, w, user_ids, B, user_features, cb + lb, &S, F);
   if (st) return st;
   WdcWs c;
   wdc_carve(ctx, S.pr, B, I, 1, S.extra, &c);
@@ -673,4 +677,12 @@ extern "C" hnm_status hnm_widedeep_refine_debug_f32(hnm_ctx* ctx, const hnm_wide
     return wd_not_instantiated(S.pr);
   HNM_LAUNCH_CHECK();
   return HNM_OK;
+}
+
+extern "C" hnm_status hnm_widedeep_refine_debug_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
+                                                    const int64_t* user_ids, int64_t B,
+                                                    const float* user_features, float* approx,
+                                                    int64_t lda, float* bound) {
+  return hnm_widedeep_refine_debug_ex_f32(ctx, w, user_ids, B, user_features, approx, lda, bound,
+                                          nullptr, nullptr, 0);
 }

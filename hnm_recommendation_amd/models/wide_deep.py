@@ -6,8 +6,19 @@ BatchNorm is folded into the next layer, layer 1 is decomposed into per-user and
 projections, and layers 2-3 run as fp32 MFMA chains fused with the top-K.
 
 * `forward(user_ids, item_ids, user_features, item_features)` (`:157-230`)
-* `predict_all_items(user_ids, user_features)` (`:232-285`)
-* `recommend(user_ids, user_features, filter_items)` (`:405-435`)
+* `predict_all_items(user_ids, user_features, item_features)` (`:232-285`)
+* `recommend(user_ids, user_features, filter_items, item_features)` (`:405-435`)
+
+Item features over the catalogue.  The reference's own configuration trains with item features
+(`configs/model/wide_deep.yaml`) but its `predict_all_items` passes `item_features=None`
+(`:275`), so it cannot rank a catalogue with such a model.  Here the catalogue calls take the
+item-feature TABLE `[num_items, num_item_features]` -- as an argument or registered once with
+`set_item_features` -- and compute the reference's `forward` over every (user, item) pair: the
+features are per item, so a HIP kernel folds them into the per-item layer-1 table and the
+per-item wide term before the scan (`csrc/widedeep_features.hip`).  `set_user_features`
+registers the `[num_users, num_user_features]` table the same way; a call without
+`user_features` then gathers the batch's rows on the device.  Neither table is part of
+`state_dict()`.
 """
 from __future__ import annotations
 
@@ -57,6 +68,9 @@ class WideDeep(RecModule):
         self.final_layer = nn.Linear(self._calculate_wide_dim() + deep_layers[-1], 1)
         self._init_weights()
         self.metrics = RecommendationMetrics(top_k=top_k)
+        # registered feature tables: they follow .to(device), and are not checkpoint state
+        self.register_buffer("item_feature_table", None, persistent=False)
+        self.register_buffer("user_feature_table", None, persistent=False)
 
     def _calculate_wide_dim(self) -> int:
         """`wide_deep.py:83-90`."""
@@ -183,19 +197,70 @@ class WideDeep(RecModule):
         ptrs = [v.data_ptr() for v in vals] + [None] * (5 - len(vals))
         return _lib.WideDeepItemFeatures(*ptrs, self.num_item_features)
 
-    def _features(self, user_features, n, device):
-        if self.num_item_features > 0:
-            raise ValueError("predict_all_items/recommend cannot use item features: the "
-                             "reference passes item_features=None there (wide_deep.py:275) and "
-                             "its deep input then does not match the network")
+    # ------------------------------------------------------------------ feature tables
+    def _table(self, table, rows, cols, what):
+        if table is None:
+            return None
+        t = torch.as_tensor(table)
+        if t.dim() != 2 or tuple(t.shape) != (rows, cols):
+            raise ValueError(f"{what} must be [{rows}, {cols}], got {list(t.shape)}")
+        return t.detach().to(device=self.final_layer.weight.device, dtype=torch.float32,
+                             copy=True).contiguous()
+
+    def set_item_features(self, table):
+        """Register the item-feature table `[num_items, num_item_features]` the catalogue calls
+        use (an fp32 copy that follows `.to(device)`; not in `state_dict()`).  `None` clears it."""
+        self.item_feature_table = self._table(table, self.num_items, self.num_item_features,
+                                              "item feature table")
+
+    def set_user_features(self, table):
+        """Register the user-feature table `[num_users, num_user_features]`: a catalogue call
+        without `user_features` gathers its batch's rows from it.  `None` clears it."""
+        self.user_feature_table = self._table(table, self.num_users, self.num_user_features,
+                                              "user feature table")
+
+    def _features(self, user_features, u):
+        """The batch's user features [B, Fu] on the device: the argument, else the registered
+        table's rows (gathered on the device)."""
         if self.num_user_features == 0:
             return None
+        n, Fu = u.numel(), self.num_user_features
         if user_features is None:
-            raise ValueError("user_features are required when num_user_features > 0")
-        f = f32c(user_features).to(device)
-        if f.shape != (n, self.num_user_features):
-            raise ValueError(f"user_features must be [{n}, {self.num_user_features}]")
+            tab = self.user_feature_table
+            if tab is None:
+                raise ValueError("user_features are required when num_user_features > 0")
+            _lib.require_gpu(tab)
+            f = torch.empty(n, Fu, dtype=torch.float32, device=u.device)
+            _lib.check(_lib.fn("hnm_gather_rows_f32")(_lib.ctx(u.device), _lib.ptr(tab),
+                                                      self.num_users, tab.stride(0), Fu,
+                                                      _lib.ptr(u), n, _lib.ptr(f), Fu),
+                       "hnm_gather_rows_f32")
+            return f
+        f = f32c(user_features).to(u.device)
+        if f.shape != (n, Fu):
+            raise ValueError(f"user_features must be [{n}, {Fu}]")
         return f
+
+    def _item_table(self, item_features, device, keep, lo=0, hi=None):
+        """(hnm_widedeep_item_features, table rows [lo, hi), ldf) of a catalogue call, or
+        (None, None, 0) for a model without item features.  An explicit table wins over the
+        registered one; it may be a strided row view (ldf = its row stride)."""
+        if self.num_item_features == 0:
+            return None, None, 0
+        t = item_features if item_features is not None else self.item_feature_table
+        if t is None:
+            raise ValueError("item_features are required when num_item_features > 0: pass the "
+                             "[num_items, num_item_features] table or set_item_features(table)")
+        t = torch.as_tensor(t).detach()
+        if t.dim() != 2 or tuple(t.shape) != (self.num_items, self.num_item_features):
+            raise ValueError(f"item_features must be the table [{self.num_items}, "
+                             f"{self.num_item_features}], got {list(t.shape)}")
+        t = t.to(device=device, dtype=torch.float32)
+        if t.stride(1) != 1 or t.stride(0) < self.num_item_features:
+            t = t.contiguous()
+        t = t[lo:hi]
+        keep.append(t)
+        return self._item_feature_weights(keep), t, t.stride(0)
 
     # ------------------------------------------------------------------ reference API
     def forward(self, user_ids, item_ids, user_features=None, item_features=None):
@@ -228,52 +293,58 @@ class WideDeep(RecModule):
         self._check(u.device, hu, hi)
         return out.squeeze()
 
-    def predict_all_items(self, user_ids, user_features=None):
-        """Dense scores [B, num_items] (`wide_deep.py:232-285`)."""
+    def predict_all_items(self, user_ids, user_features=None, item_features=None):
+        """Dense scores [B, num_items] (`wide_deep.py:232-285`); `item_features` is the
+        [num_items, num_item_features] table (default: the registered one)."""
         w, keep = self._weights()
         u, hu = self._ids(user_ids, self.num_users)
-        f = self._features(user_features, u.numel(), u.device)
+        f = self._features(user_features, u)
+        itf, tab, ldf = self._item_table(item_features, u.device, keep)
         out = torch.empty(u.numel(), self.num_items, dtype=torch.float32, device=u.device)
         c = _lib.ctx(u.device)
-        _lib.check(_lib.fn("hnm_widedeep_scores_f32")(c, w, _lib.ptr(u), u.numel(), _lib.ptr(f),
-                                                      _lib.ptr(out), out.stride(0)),
-                   "hnm_widedeep_scores_f32")
+        _lib.check(_lib.fn("hnm_widedeep_scores_ex_f32")(
+            c, w, _lib.ptr(u), u.numel(), _lib.ptr(f), _lib.ptr(out), out.stride(0),
+            None if itf is None else C.byref(itf), _lib.ptr(tab), ldf),
+            "hnm_widedeep_scores_ex_f32")
         self._check(u.device, hu)
         return out
 
     def recommend_with_scores(self, user_ids, user_features=None,
                               filter_items: Optional[Dict[int, set]] = None,
-                              k: Optional[int] = None):
+                              k: Optional[int] = None, item_features=None):
         k = self.top_k if k is None else k
         w, keep = self._weights()
         u, hu = self._ids(user_ids, self.num_users)
-        f = self._features(user_features, u.numel(), u.device)
+        f = self._features(user_features, u)
+        itf, tab, ldf = self._item_table(item_features, u.device, keep)
         mptr, midx = filter_csr(u, filter_items, self.num_items, u.device)
         kk = min(k, self.num_items)
         if kk <= 0:
             return empty_topk(k, u)
         if kk > 64:
-            return dense_topk(self.predict_all_items(u, user_features), kk, mptr, midx)
+            return dense_topk(self.predict_all_items(u, f, tab), kk, mptr, midx)
         out_v = torch.empty(u.numel(), kk, dtype=torch.float32, device=u.device)
         out_i = torch.empty(u.numel(), kk, dtype=torch.int64, device=u.device)
         c = _lib.ctx(u.device)
-        _lib.check(_lib.fn("hnm_widedeep_topk_f32")(c, w, _lib.ptr(u), u.numel(), _lib.ptr(f),
-                                                    _lib.ptr(mptr), _lib.ptr(midx), kk,
-                                                    _lib.ptr(out_v), _lib.ptr(out_i)),
-                   "hnm_widedeep_topk_f32")
+        _lib.check(_lib.fn("hnm_widedeep_topk_ex_f32")(
+            c, w, _lib.ptr(u), u.numel(), _lib.ptr(f), _lib.ptr(mptr), _lib.ptr(midx), kk,
+            _lib.ptr(out_v), _lib.ptr(out_i), None if itf is None else C.byref(itf),
+            _lib.ptr(tab), ldf), "hnm_widedeep_topk_ex_f32")
         self._check(u.device, hu)
         return out_v, out_i
 
     def _validation_topk(self, batch):
         """`predict_all_items(user_ids, user_features)` + torch.topk of the reference's
-        validation_step (wide_deep.py:314-332), as the fused top-K."""
+        validation_step (wide_deep.py:314-332), as the fused top-K (item features: the
+        registered table)."""
         return self.recommend_with_scores(batch["user_ids"], batch.get("user_features"),
                                           k=self.top_k)[1]
 
     def recommend(self, user_ids, user_features=None,
-                  filter_items: Optional[Dict[int, set]] = None):
+                  filter_items: Optional[Dict[int, set]] = None, item_features=None):
         """Top-`top_k` item ids per user (`wide_deep.py:405-435`)."""
         self._check_top_k()
         self.eval()
         with torch.no_grad():
-            return self.recommend_with_scores(user_ids, user_features, filter_items)[1]
+            return self.recommend_with_scores(user_ids, user_features, filter_items,
+                                              item_features=item_features)[1]

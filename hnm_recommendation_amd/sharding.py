@@ -410,7 +410,9 @@ class dot_shard_topk:
 
 def widedeep_shard_topk(model, lo: int, hi: int, k: int, history=None) -> LocalTopK:
     """Fused Wide&Deep score + top-K over item rows [lo, hi) of `model` (a WideDeep on a GPU);
-    `history` (a UserHistory) masks each user's history items."""
+    `history` (a UserHistory) masks each user's history items.  A model with features uses its
+    registered tables (`set_user_features` / `set_item_features`): the batch's user rows are
+    gathered on the device, the shard gets item-feature rows [lo, hi)."""
     def run(user_ids: torch.Tensor):
         w, keep = model._weights()
         w = _lib.WideDeepWeights.from_buffer_copy(w)
@@ -419,15 +421,17 @@ def widedeep_shard_topk(model, lo: int, hi: int, k: int, history=None) -> LocalT
         w.wide_item = w.wide_item + lo * 4
         w.num_items = hi - lo
         u = user_ids.to(torch.int64).contiguous()
+        f = model._features(None, u)
+        itf, tab, ldf = model._item_table(None, u.device, keep, lo, hi)
         mp, mi = _mask(history, u, lo, hi)
         kk = min(k, hi - lo)
         out_v = torch.empty(u.numel(), kk, dtype=torch.float32, device=u.device)
         out_i = torch.empty(u.numel(), kk, dtype=torch.int64, device=u.device)
         c = _lib.ctx(u.device)
-        _lib.check(_lib.fn("hnm_widedeep_topk_f32")(c, w, _lib.ptr(u), u.numel(), None,
-                                                    _lib.ptr(mp), _lib.ptr(mi), kk,
-                                                    _lib.ptr(out_v), _lib.ptr(out_i)),
-                   "hnm_widedeep_topk_f32")
+        _lib.check(_lib.fn("hnm_widedeep_topk_ex_f32")(
+            c, w, _lib.ptr(u), u.numel(), _lib.ptr(f), _lib.ptr(mp), _lib.ptr(mi), kk,
+            _lib.ptr(out_v), _lib.ptr(out_i), None if itf is None else C.byref(itf),
+            _lib.ptr(tab), ldf), "hnm_widedeep_topk_ex_f32")
         return _pad(out_v, out_i, k)
     return run
 

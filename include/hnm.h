@@ -341,7 +341,8 @@ hnm_status hnm_ncf_deep_prefilter_debug_f32(hnm_ctx* ctx, const hnm_ncf_deep_wei
  * where wide_user / wide_item / wide_feat / final_deep are the segments [0, U), [U, U+I),
  * [U+I, U+I+F) and [wide_dim, ...) of final_layer.weight[0] (item rows may be a shard).
  * Towers of 2 (w3 == NULL, l3 == 0) or 3 layers, widths <= 512 / 256 / 128; deep input
- * [e_u; e_i] (+ deep_user_features(f_u) when num_user_features > 0). */
+ * [e_u; e_i] (+ deep_user_features(f_u) when num_user_features > 0) (+ deep_item_features(f_i):
+ * the _ex entries below). */
 typedef struct {
   const float* deep_user;  /* [num_users, d] */
   const float* deep_item;  /* [num_items, d] */
@@ -413,6 +414,30 @@ hnm_status hnm_widedeep_pair_scores_ex_f32(hnm_ctx* ctx, const hnm_widedeep_weig
                                            const int64_t* user_ids, const int64_t* item_ids,
                                            const float* user_features, const float* item_features,
                                            int64_t n, float* out);
+/* Catalogue scoring of a model with item features: hnm_widedeep_topk_f32 /
+ * hnm_widedeep_scores_f32 plus the item-feature weights and the item-feature TABLE
+ * item_features [w->num_items, Fi] (fp32, device, leading dimension ldf >= Fi; row i = the
+ * features of item row i of this call's tables -- a row shard points at its first row, as for
+ * deep_item / wide_item).  The features are per item, so they fold into the per-item layer-1
+ * table and the per-item wide term before the scan:
+ *   Q_i  = W1[:, d:2d] e_i + W1[:, c:c+d] (dif_w f_i + dif_b),  c = (2 + [Fu > 0]) d
+ *   wI_i = wide_item[i] + wide_feat . (wif_w f_i + wif_b)
+ * (the reference passes item_features=None in predict_all_items, wide_deep.py:275, and cannot
+ * score such a model; this is its forward over every (user, item) pair).  w->l1_in must be
+ * (2 + [Fu > 0] + 1) d; item_features, dif_w and dif_b must not be NULL (HNM_EINVAL); wif_w /
+ * wide_feat may be NULL (use_wide_features=False: no wide item-feature term).  itf == NULL or
+ * itf->num_item_features == 0: exactly the entries without _ex. */
+hnm_status hnm_widedeep_topk_ex_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
+                                    const int64_t* user_ids, int64_t B, const float* user_features,
+                                    const int64_t* mask_ptr, const int32_t* mask_idx, int k,
+                                    float* out_val, int64_t* out_idx,
+                                    const hnm_widedeep_item_features* itf,
+                                    const float* item_features, int64_t ldf);
+hnm_status hnm_widedeep_scores_ex_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
+                                      const int64_t* user_ids, int64_t B,
+                                      const float* user_features, float* out, int64_t ldo,
+                                      const hnm_widedeep_item_features* itf,
+                                      const float* item_features, int64_t ldf);
 
 /* ---- top-K merge (item partitions, item shards across GPUs) ------------------------
  * Candidates of row b: for g < G: cand[g*gstride + b*bstride + j], j < kc (value, global
@@ -477,6 +502,19 @@ hnm_status hnm_widedeep_refine_debug_f32(hnm_ctx* ctx, const hnm_widedeep_weight
                                          const int64_t* user_ids, int64_t B,
                                          const float* user_features, float* approx, int64_t lda,
                                          float* bound);
+/* Both diagnostics for a model with item features (see hnm_widedeep_topk_ex_f32). */
+hnm_status hnm_widedeep_prefilter_debug_ex_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
+                                               const int64_t* user_ids, int64_t B,
+                                               const float* user_features, float* approx,
+                                               int64_t lda, float* bound,
+                                               const hnm_widedeep_item_features* itf,
+                                               const float* item_features, int64_t ldf);
+hnm_status hnm_widedeep_refine_debug_ex_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
+                                            const int64_t* user_ids, int64_t B,
+                                            const float* user_features, float* approx,
+                                            int64_t lda, float* bound,
+                                            const hnm_widedeep_item_features* itf,
+                                            const float* item_features, int64_t ldf);
 
 /* ---- a11: batch mask from a device-resident history CSR --------------------------------
  * The purchase-history filter (serve.py:350-352; the filter_items loop of every recommend,
