@@ -5,6 +5,7 @@
 
 #include "hnm_device.h"
 #include "hnm_internal.h"
+#include "linear_mfma.h"
 
 static thread_local char g_err[512] = "";
 
@@ -39,6 +40,7 @@ extern "C" hnm_status hnm_ctx_create(int device, hnm_ctx** out) {
 #define HNM_LINEAR_MFMA_DEFAULT 1
 #endif
   c->linear_mfma = HNM_LINEAR_MFMA_DEFAULT;
+  c->ncf_tables = 1;
   if (hipMalloc((void**)&c->err_dev, 64) != hipSuccess) {
     free(c);
     hnm_set_error("hnm_ctx_create: hipMalloc of the error word failed");
@@ -114,6 +116,9 @@ extern "C" hnm_status hnm_ctx_set_option(hnm_ctx* ctx, int option, int64_t value
       return HNM_OK;
     case HNM_OPT_LINEAR_MFMA:
       ctx->linear_mfma = value != 0;
+      return HNM_OK;
+    case HNM_OPT_NCF_TABLES:
+      ctx->ncf_tables = value != 0;
       return HNM_OK;
     default:
       hnm_set_error("hnm_ctx_set_option: unknown option %d", option);
@@ -322,8 +327,7 @@ extern "C" hnm_status hnm_gather_rows_f32(hnm_ctx* ctx, const float* table, int6
 // or 16 for short inputs -- a batch of users -- so the grid still covers the CUs), K in
 // chunks of 32 staged through LDS; each thread owns a TM/16 x 4 output patch.  fp32 FMA
 // chain in k order whatever TM (a per-item / per-user precompute: <1 % of any scoring kernel).
-#define LIN_TN 64
-#define LIN_TK 32
+// (LIN_TN = 64 outputs, LIN_TK = 32: linear_mfma.h)
 // VEC (K, ldx, ldw multiples of 4, 16-B aligned X and W): 16-B global loads, and the compute
 // loop reads its x / w operands as float4 from the 16-B-aligned LDS rows (2 LDS reads per 16
 // FMAs instead of 8); the FMA chain per output is the same k-ordered one either way.
@@ -450,47 +454,14 @@ __global__ __launch_bounds__(256) void linear_rows_mfma_kernel(
     const float* __restrict__ X, int64_t ldx, const int64_t* __restrict__ ids, int64_t x_rows,
     int64_t M, int K, const float* __restrict__ W, int64_t ldw, const float* __restrict__ bias,
     int N, float* __restrict__ Y, int64_t ldy, int pair_permute, unsigned* err) {
-  constexpr int RS = LIN_TK + 1;  // LDS row stride (floats): rows spread over the banks
-  __shared__ float xs[64 * RS];   // [row][k] of the chunk
-  __shared__ float ws[64 * RS];   // [output][k]
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  __shared__ float xs[64 * LIN_RS];  // [row][k] of the chunk
+  __shared__ float ws[64 * LIN_RS];  // [output][k]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 31, h = lane >> 5;
   const int64_t m0 = (int64_t)blockIdx.x * 64;
   const int n0 = blockIdx.y * LIN_TN;
   const int wr = 32 * (wave >> 1), wc = 32 * (wave & 1);
-  f32x16 acc = {};
-  for (int k0 = 0; k0 < K; k0 += LIN_TK) {
-    for (int e = t; e < 64 * LIN_TK / 4; e += 256) {
-      const int rr = e / (LIN_TK / 4), kq = 4 * (e % (LIN_TK / 4));
-      const int64_t m = m0 + rr;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (m < M) {
-        const int64_t src = ids ? ids[m] : m;
-        if (src < 0 || src >= x_rows) {
-          if (kq == 0) hnm_flag(err, HNM_ERR_OOB);
-          v = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""),
-                          __builtin_nanf(""));
-        } else {
-          v = *reinterpret_cast<const float4*>(X + src * ldx + k0 + kq);
-        }
-      }
-      float* xr = xs + rr * RS + kq;
-      xr[0] = v.x; xr[1] = v.y; xr[2] = v.z; xr[3] = v.w;
-    }
-    for (int e = t; e < LIN_TN * LIN_TK / 4; e += 256) {
-      const int nn = e / (LIN_TK / 4), kq = 4 * (e % (LIN_TK / 4));
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (n0 + nn < N) v = *reinterpret_cast<const float4*>(W + (int64_t)(n0 + nn) * ldw + k0 + kq);
-      float* wr4 = ws + nn * RS + kq;
-      wr4[0] = v.x; wr4[1] = v.y; wr4[2] = v.z; wr4[3] = v.w;
-    }
-    __syncthreads();
-    const float* xa = xs + (wr + i) * RS + h;  // A[i][h] of step s: row wr + i, k = 2 s + h
-    const float* wb = ws + (wc + i) * RS + h;  // B[h][j = i]: output wc + i, k = 2 s + h
-#pragma unroll
-    for (int st = 0; st < LIN_TK / 2; ++st) acc = mfma32x32x2(xa[2 * st], wb[2 * st], acc);
-    __syncthreads();
-  }
+  const f32x16 acc = linear_mfma_tile(X, ldx, ids, x_rows, M, K, W, ldw, N, m0, n0, xs, ws, err);
   const int n = n0 + wc + i;
   if (n >= N) return;
   const float bn = bias ? bias[n] : 0.f;

@@ -519,7 +519,7 @@ __global__ __launch_bounds__(256) void gather_scale_kernel(const float* __restri
   if (!ok && lane == 0) hnm_flag(err, HNM_ERR_OOB);
   for (int c = lane; c < ldo; c += 64) {
     const int o = permute ? (c & 1) * (ldo / 2) + (c >> 1) : c;
-    out[r * ldo + o] = (ok && c < d) ? tab[id * ld + c] * s[c] : 0.f;
+    out[r * ldo + o] = ncf_gather_scale(tab, id, ld, d, s, c, ok);
   }
 }
 
@@ -622,10 +622,20 @@ struct NcfCall {
   void* extra;
 };
 
+// A call that goes on to the certified two-layer path (ncf_cert_begin / ncf_cert_debug on
+// `extra` = ncf_cert_bytes(B, I, K, .., strided) bytes of scratch): where the shape allows and
+// HNM_OPT_NCF_TABLES is on, ncf_tables builds the tables and the bound statistics of their rows
+// in one launch (ncf_cert_tables).
+struct NcfCertUse {
+  int K;
+  bool strided;
+};
+
 // fill = false: only re-derive the pointers into the workspace the begin phase of a
 // two-phase call filled (hnm_ncf_topk_finish_f32).
 static hnm_status ncf_tables(hnm_ctx* ctx, const hnm_ncf_weights* w, const int64_t* ids,
-                             int64_t B, size_t extra, NcfCall* out, bool fill = true) {
+                             int64_t B, size_t extra, NcfCall* out, bool fill = true,
+                             const NcfCertUse* cert = nullptr) {
   const bool big = w->h1 > 64 || w->mf > 64;  // generic kernel; else the 32-user kernels
   const int H1P = big ? 128 : 64, GW = big ? 128 : 64;
   const int64_t I = w->num_items;
@@ -658,6 +668,14 @@ static hnm_status ncf_tables(hnm_ctx* ctx, const hnm_ncf_weights* w, const int64
   }
   out->t = {Pu, WGu, qcache ? w->item_proj : Qi, G, ldg};
   if (!fill) return HNM_OK;
+  // one launch for the tables and their statistics (the scratch is carved before the tables are
+  // filled); every other shape keeps the separate launches below
+  const auto al16 = [](const void* p) { return (uintptr_t)p % 16 == 0; };
+  if (cert && ctx->ncf_tables && !big && !gcopy && w->h0 % 32 == 0 && al16(w->mlp_user) &&
+      al16(w->mlp_item) && al16(w->w1)) {
+    out->t.stats = true;
+    return ncf_cert_tables(ctx, w, ids, B, Pu, WGu, Qi, cert->K, out->extra, cert->strided);
+  }
   if (w->h1 < H1P) {
     HNM_HIP_CHECK(hipMemsetAsync(Pu, 0, szP, ctx->stream));
     if (!qcache) HNM_HIP_CHECK(hipMemsetAsync(Qi, 0, szQ, ctx->stream));
@@ -704,7 +722,8 @@ static hnm_status ncf_common(hnm_ctx* ctx, const hnm_ncf_weights* w, const int64
   const size_t extra =
       cert ? ncf_cert_bytes(B, I, K, ctx->num_cus, ncf_cert_wg(ctx), strided) : 2 * szC;
   NcfCall c;
-  st = ncf_tables(ctx, w, ids, B, extra, &c);
+  const NcfCertUse use{K, strided};
+  st = ncf_tables(ctx, w, ids, B, extra, &c, true, cert ? &use : nullptr);
   if (st) return st;
   if (cert) return ncf_cert_topk(ctx, w, c.t, B, mptr, midx, K, c.extra, strided, ov, oi);
   float* cv = (float*)c.extra;
@@ -778,9 +797,10 @@ static hnm_status ncf_topk_begin(hnm_ctx* ctx, const hnm_ncf_weights* w, const i
   const bool strided = ctx->strided != 0;
   if (cert) {
     NcfCall c;
+    const NcfCertUse use{k, strided};
     st = ncf_tables(ctx, w, user_ids, B,
                     ncf_cert_bytes(B, w->num_items, k, ctx->num_cus, ncf_cert_wg(ctx), strided),
-                    &c);
+                    &c, true, &use);
     if (st) return st;
     st = ncf_cert_begin(ctx, w, c.t, B, mask_ptr, mask_idx, k, c.extra, strided, lower_bound,
                         lists);
@@ -874,8 +894,10 @@ extern "C" hnm_status hnm_ncf_prefilter_debug_f32(hnm_ctx* ctx, const hnm_ncf_we
               "ncf_prefilter_debug: the f16 pre-filter covers h1 <= 64, mf <= 64, < 2^25 items");
   if (B <= 0) return HNM_OK;
   NcfCall c;
+  const NcfCertUse use{1, false};
   st = ncf_tables(ctx, w, user_ids, B,
-                  ncf_cert_bytes(B, w->num_items, 1, ctx->num_cus, ncf_cert_wg(ctx), false), &c);
+                  ncf_cert_bytes(B, w->num_items, 1, ctx->num_cus, ncf_cert_wg(ctx), false), &c,
+                  true, &use);
   if (st) return st;
   return ncf_cert_debug(ctx, w, c.t, B, c.extra, approx, lda, bound);
 }

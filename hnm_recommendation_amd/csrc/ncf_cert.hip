@@ -33,9 +33,19 @@
 // Scaling: every f16 operand is scaled by a power of two so its magnitude is <= 1 (layer-1
 // inputs <= 0.5, which also makes the packed add's [0,1] CLAMP an exact ReLU:
 // v_pk_add_f16 ... clamp).  Scores are compared in the scaled unit s1*sw*sm.
+//
+// Per-call kernels before the first sample pass (two-layer tower, HNM_OPT_NCF_TABLES = 1):
+//   ncf_tables_kernel    P_u, wp * g_u, Q_i (fp32) and A_u, C_u, B_i, D_i + the maxima's partials
+//   cert_scales_kernel   one workgroup: partials and weight statistics -> CertParams
+//   cert_convert_kernel  f16 copies P16 / WG16 / Q16 / G16 / weights, Bs / Cs in test units
+// HNM_OPT_NCF_TABLES = 0, deep towers, padded GMF copies, h0 % 32 != 0 or unaligned tables: the
+// tables by hnm_linear_rows_f32 (users, items) and gather_scale_kernel (ncf.hip ncf_tables), then
+// cert_stats_kernel, cert_scales_kernel, cert_convert_kernel (deep towers: cert_deep_u_kernel
+// first).  Both routes leave bitwise the same tables, bound terms and CertParams.
 #include <algorithm>
 
 #include "hnm_device.h"
+#include "linear_mfma.h"
 #include "ncf_internal.h"
 #include "sample_kth.h"
 
@@ -110,6 +120,135 @@ __device__ __forceinline__ float wave_max(float x) {
 __device__ __forceinline__ int korig(int t) { return 2 * (t & 31) + (t >> 5); }
 
 // ------------------------------------------------------------------ bound statistics
+// The pieces of cert_stats_kernel that ncf_tables_kernel shares (one definition of every sum and
+// maximum: the statistics are bitwise the same whichever kernel forms them).
+
+// vs[t] = v_k = sum_j |wm_j| |W2_jk| of the layer-1 unit k stored at pair-permuted position t
+__device__ __forceinline__ void cert_fill_vs(float* vs, const float* __restrict__ W2, int h1,
+                                             int h2, const float* __restrict__ wm) {
+  const int tid = threadIdx.x;
+  if (tid < 64) {
+    float v = 0.f;
+    const int k = korig(tid);
+    if (k < h1)
+      for (int j = 0; j < h2; ++j) v += fabsf(wm[j]) * fabsf(W2[j * h1 + k]);
+    vs[tid] = v;
+  }
+}
+
+// The 8 wave sums of v8[0..7] as one reduce-scatter butterfly: each xor step halves the values a
+// lane carries (10 shuffles instead of 48); every sum is formed along the same xor 32, 16, ..., 1
+// pairing as wave_sum, so bitwise the same.  Returns sum number cert_sum8_idx(lane).
+__device__ __forceinline__ float cert_sum8(const float (&v8)[8], int lane) {
+  const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
+  float w4[4], w2[2];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    w4[q] = (b5 ? v8[2 * q + 1] : v8[2 * q]) + __shfl_xor(b5 ? v8[2 * q] : v8[2 * q + 1], 32);
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    w2[q] = (b4 ? w4[2 * q + 1] : w4[2 * q]) + __shfl_xor(b4 ? w4[2 * q] : w4[2 * q + 1], 16);
+  float w1 = (b3 ? w2[1] : w2[0]) + __shfl_xor(b3 ? w2[0] : w2[1], 8);
+  w1 += __shfl_xor(w1, 4);
+  w1 += __shfl_xor(w1, 2);
+  w1 += __shfl_xor(w1, 1);
+  return w1;
+}
+__device__ __forceinline__ int cert_sum8_idx(int lane) {  // the sum this lane holds
+  return ((lane & 32) ? 1 : 0) + ((lane & 16) ? 2 : 0) + ((lane & 8) ? 4 : 0);
+}
+
+// Four items i0 + u * stride (u = 0..3; the wave holds |Q| and G of each, one column a lane):
+// B_i = v . |Q_i|, D_i = ||g_i||_2 and the running maxima of |Q|, |G|, B, D.
+__device__ __forceinline__ void cert_item_stats4(float vt, const float (&aq)[4],
+                                                 const float (&g)[4], int64_t i0, int64_t stride,
+                                                 int64_t I, int lane, float* __restrict__ Bi,
+                                                 float* __restrict__ Di, float& m0, float& m1,
+                                                 float& m2, float& m3) {
+  float v8[8];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    v8[u] = vt * aq[u];
+    v8[4 + u] = g[u] * g[u];
+    if (i0 + u * stride < I) {  // uniform
+      m0 = nmax(m0, aq[u]);
+      m1 = nmax(m1, fabsf(g[u]));
+    }
+  }
+  const float w1 = cert_sum8(v8, lane);
+  const int idx = cert_sum8_idx(lane);
+  const int64_t i = i0 + (idx & 3) * stride;
+  if (i < I) {
+    if (idx < 4) {
+      m2 = nmax(m2, w1);
+      if ((lane & 7) == 0) Bi[i] = w1;
+    } else {
+      const float dq = sqrtf(w1);
+      m3 = nmax(m3, dq);
+      if ((lane & 7) == 0) Di[i] = dq;
+    }
+  }
+}
+
+// One batch row (|P_u| and wp * g_u, one column a lane): A_u = v . |P_u|, C_u = ||wp * g_u||_2
+// and the running maxima of |P| and |WG|.
+__device__ __forceinline__ void cert_user_stats(float vt, float ap, float wg, int64_t b, int lane,
+                                                float* __restrict__ Au, float* __restrict__ Cu,
+                                                float& m0, float& m1) {
+  m0 = nmax(m0, ap);
+  m1 = nmax(m1, fabsf(wg));
+  const float a = wave_sum(vt * ap), c2 = wave_sum(wg * wg);
+  if (lane == 0) {
+    Au[b] = a;
+    Cu[b] = sqrtf(c2);
+  }
+}
+
+// cert_fill_vs with W2 and wm staged through LDS first (scr: h2 * h1 + 32 <= 2,080 floats): one
+// round of independent loads in place of h2 dependent steps; the sum itself is cert_fill_vs's,
+// term by term in j order.  Ends with a barrier (vs is set, scr is free).
+__device__ __forceinline__ void cert_fill_vs_staged(float* vs, const float* __restrict__ W2,
+                                                    int h1, int h2, const float* __restrict__ wm,
+                                                    float* scr) {
+  const int tid = threadIdx.x;
+  float* const wms = scr + h2 * h1;
+  for (int e = tid; e < h2 * h1; e += 256) scr[e] = W2[e];
+  if (tid < h2) wms[tid] = wm[tid];
+  __syncthreads();
+  if (tid < 64) {
+    float v = 0.f;
+    const int k = korig(tid);
+    if (k < h1)
+      for (int j = 0; j < h2; ++j) v += fabsf(wms[j]) * fabsf(scr[j * h1 + k]);
+    vs[tid] = v;
+  }
+  __syncthreads();
+}
+
+// The workgroup's four maxima -> part[4 * slot ..] (per-block partials, no same-address atomics;
+// reduced by cert_scales_kernel).  Called by the whole workgroup.
+__device__ __forceinline__ void cert_block_maxima(float m0, float m1, float m2, float m3,
+                                                  float (*red)[4], float* __restrict__ part,
+                                                  int slot) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  m0 = wave_max(m0);
+  m1 = wave_max(m1);
+  m2 = wave_max(m2);
+  m3 = wave_max(m3);
+  if (lane == 0) {
+    red[wave][0] = m0;
+    red[wave][1] = m1;
+    red[wave][2] = m2;
+    red[wave][3] = m3;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    float m = red[0][tid];
+    for (int w = 1; w < 4; ++w) m = nmax(m, red[w][tid]);
+    part[slot * 4 + tid] = m;
+  }
+}
+
 __global__ __launch_bounds__(256) void cert_stats_kernel(NcfTabs t, int64_t B, int64_t I, int mf,
                                                          const float* __restrict__ W2, int h1,
                                                          int h2, const float* __restrict__ wm,
@@ -122,13 +261,7 @@ __global__ __launch_bounds__(256) void cert_stats_kernel(NcfTabs t, int64_t B, i
   __shared__ float vs[64];
   __shared__ float red[4][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < 64) {
-    float v = 0.f;
-    const int k = korig(tid);
-    if (k < h1)
-      for (int j = 0; j < h2; ++j) v += fabsf(wm[j]) * fabsf(W2[j * h1 + k]);
-    vs[tid] = v;
-  }
+  cert_fill_vs(vs, W2, h1, h2, wm);
   __syncthreads();
   const float vt = vs[lane];
   float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;  // items: Q, G, B, D / users: P, WG
@@ -144,75 +277,148 @@ __global__ __launch_bounds__(256) void cert_stats_kernel(NcfTabs t, int64_t B, i
         aq[u] = fabsf(t.Qi[i * 64 + lane]);
         g[u] = lane < mf ? t.G[i * t.ldg + lane] : 0.f;
       }
-      // the 8 wave sums (vt . |q|, |g|^2 of the 4 items) as one reduce-scatter butterfly: each
-      // xor step halves the values a lane carries (10 shuffles instead of 48); every sum is
-      // formed along the same xor 32, 16, ..., 1 pairing as wave_sum, so bitwise the same
-      float v8[8];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        v8[u] = vt * aq[u];
-        v8[4 + u] = g[u] * g[u];
-        if (i0 + u * stride < I) {  // uniform
-          m0 = nmax(m0, aq[u]);
-          m1 = nmax(m1, fabsf(g[u]));
-        }
-      }
-      const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
-      float w4[4], w2[2];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        w4[q] = (b5 ? v8[2 * q + 1] : v8[2 * q]) + __shfl_xor(b5 ? v8[2 * q] : v8[2 * q + 1], 32);
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-        w2[q] = (b4 ? w4[2 * q + 1] : w4[2 * q]) + __shfl_xor(b4 ? w4[2 * q] : w4[2 * q + 1], 16);
-      float w1 = (b3 ? w2[1] : w2[0]) + __shfl_xor(b3 ? w2[0] : w2[1], 8);
-      w1 += __shfl_xor(w1, 4);
-      w1 += __shfl_xor(w1, 2);
-      w1 += __shfl_xor(w1, 1);
-      const int idx = (b5 ? 1 : 0) + (b4 ? 2 : 0) + (b3 ? 4 : 0);  // the sum this lane holds
-      const int64_t i = i0 + (idx & 3) * stride;
-      if (i < I) {
-        if (idx < 4) {
-          m2 = nmax(m2, w1);
-          if ((lane & 7) == 0) Bi[i] = w1;
-        } else {
-          const float dq = sqrtf(w1);
-          m3 = nmax(m3, dq);
-          if ((lane & 7) == 0) Di[i] = dq;
-        }
-      }
+      cert_item_stats4(vt, aq, g, i0, stride, I, lane, Bi, Di, m0, m1, m2, m3);
     }
   } else {
     const int ub = (int)blockIdx.x - item_blocks;
-    for (int64_t b = (int64_t)ub * 4 + wave; b < B; b += (int64_t)user_blocks * 4) {
-      const float ap = fabsf(t.Pu[b * 64 + lane]);
-      const float wg = t.WGu[b * 64 + lane];
-      m0 = nmax(m0, ap);
-      m1 = nmax(m1, fabsf(wg));
-      const float a = wave_sum(vt * ap), c2 = wave_sum(wg * wg);
-      if (lane == 0) {
-        Au[b] = a;
-        Cu[b] = sqrtf(c2);
+    for (int64_t b = (int64_t)ub * 4 + wave; b < B; b += (int64_t)user_blocks * 4)
+      cert_user_stats(vt, fabsf(t.Pu[b * 64 + lane]), t.WGu[b * 64 + lane], b, lane, Au, Cu, m0,
+                      m1);
+  }
+  cert_block_maxima(m0, m1, m2, m3, red, part, blockIdx.x);
+}
+
+// The per-call tables AND the bound statistics of their rows in one launch (HNM_OPT_NCF_TABLES;
+// two-layer towers, h1 <= 64, mf <= 64 a multiple of 4, h0 a multiple of 32, 16-B aligned
+// tables).  In place of linear_rows (users), linear_rows (items), gather_scale and
+// cert_stats_kernel: Q_i is written once and never read back for its statistics, G is read once.
+// Heterogeneous blocks as cert_stats_kernel's, each over 64-row tiles (grid-stride), partials in
+// cert_stats_kernel's layout (item blocks' first):
+//   item blocks: the Q_i tile by linear_mfma_tile (linear_rows_mfma_kernel's chain: the rows are
+//     bitwise hnm_linear_rows_f32's), staged pair-permuted through the LDS the k-loop released,
+//     stored fp32 (re-scoring and the exact fallback read it), and B_i, D_i and the maxima of
+//     |Q|, |G|, B, D from the staged tile and the items' G rows (loads issued before the k-loop).
+//     a.item_proj set (the caller's cached projection): no projection, the tile is read from it.
+//   user blocks: P_u = W1u m_u + b1 (ids gathered, out-of-range ids flagged, their rows NaN),
+//     wp * g_u (gather_scale_kernel's product), A_u, C_u and the maxima of |P|, |WG|.
+// Columns h1..63 of P / Q are written as zero (no memset of the tables).  Every sum and maximum
+// is cert_stats_kernel's own (the functions above), so Bi, Di, Au, Cu and the reduced maxima are
+// bitwise the separate launches'.
+struct NcfTablesArgs {
+  const float* mlp_user;   // [num_users, h0]
+  const float* mlp_item;   // [I, h0]
+  const float* gmf_user;   // [num_users, mf]
+  const float* w1;         // [h1, 2 h0]
+  const float* b1;         // [h1]
+  const float* wp;         // [mf] GMF part of the prediction weights
+  const float* item_proj;  // [I, 64] cached Q (nullptr: computed and written to Qi)
+  const int64_t* ids;      // [B]
+  int64_t num_users;
+  int h0, h1, mf;
+  float* Pu;               // [B, 64]
+  float* WGu;              // [B, 64]
+  float* Qi;               // [I, 64]
+  const float* G;          // [I, ldg]
+  int64_t ldg;
+};
+
+__global__ __launch_bounds__(256) void ncf_tables_kernel(
+    NcfTablesArgs a, int64_t B, int64_t I, const float* __restrict__ W2, int h2,
+    const float* __restrict__ wm, float* __restrict__ Au, float* __restrict__ Cu,
+    float* __restrict__ Bi, float* __restrict__ Di, float* __restrict__ part, int item_blocks,
+    int user_blocks, unsigned* err) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * 64 * LIN_RS];  // xs | ws, then the tile
+  __shared__ float vs[64];
+  __shared__ float red[4][4];
+  float* const xs = lds;
+  float* const ws = lds + 64 * LIN_RS;
+  float* const stage = lds;  // [64 rows][64 pair-permuted columns] (<= the k-loop's 2 * 64 * 33)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = lane >> 5;
+  const int wr = 32 * (wave >> 1);
+  const int n = 32 * (wave & 1) + (lane & 31);  // this lane's output unit in the k-loop's tile
+  const int nc = (n & 1) * 32 + (n >> 1);        // its pair-permuted column
+  cert_fill_vs_staged(vs, W2, a.h1, h2, wm, lds);
+  const float vt = vs[lane];
+  float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;  // items: Q, G, B, D / users: P, WG
+  const int r0 = wave * 16;  // the wave's rows of a tile for the statistics
+  // the (few, one-tile) user blocks are dispatched first, so they run beside the item blocks and
+  // not behind them; the partials keep cert_stats_kernel's layout, item blocks first
+  const bool items = (int)blockIdx.x >= user_blocks;
+  const int blk = items ? (int)blockIdx.x - user_blocks : (int)blockIdx.x;
+  if (items) {
+    const int64_t ntiles = hnm_cdiv(I, 64);
+    for (int64_t tile = blk; tile < ntiles; tile += item_blocks) {
+      const int64_t t0 = tile * 64;
+      float g[16];  // G of the wave's rows, issued before the k-loop (rows past I: unused zeros)
+      const float* gp = a.G + (t0 + r0) * a.ldg + lane;
+      const int nrow = (int)std::min<int64_t>(16, I - t0 - r0);  // may be <= 0
+#pragma unroll
+      for (int r = 0; r < 16; ++r) g[r] = (lane < a.mf && r < nrow) ? gp[r * a.ldg] : 0.f;
+      if (!a.item_proj) {
+        const f32x16 acc = linear_mfma_tile(a.mlp_item, a.h0, nullptr, I, I, a.h0, a.w1 + a.h0,
+                                            2 * a.h0, a.h1, t0, 0, xs, ws, err);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          stage[(wr + mfma32_row(r, h)) * 64 + nc] = n < a.h1 ? acc[r] : 0.f;
+        __syncthreads();
       }
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const int64_t i0 = t0 + r0 + 4 * q4;
+        if (i0 < I) {  // uniform
+          float aq[4], g4[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            float qv;
+            if (a.item_proj) {
+              qv = a.item_proj[std::min<int64_t>(i0 + u, I - 1) * 64 + lane];
+            } else {
+              qv = stage[(r0 + 4 * q4 + u) * 64 + lane];
+              if (i0 + u < I) a.Qi[(i0 + u) * 64 + lane] = qv;
+            }
+            aq[u] = fabsf(qv);
+            g4[u] = g[4 * q4 + u];
+          }
+          cert_item_stats4(vt, aq, g4, i0, 1, I, lane, Bi, Di, m0, m1, m2, m3);
+        }
+      }
+      __syncthreads();  // the tile is consumed: the next k-loop may stage over it
+    }
+  } else {
+    const int64_t ntiles = hnm_cdiv(B, 64);
+    const int kc = korig(lane);  // the GMF column stored at pair-permuted position `lane`
+    for (int64_t tile = blk; tile < ntiles; tile += user_blocks) {
+      const int64_t t0 = tile * 64;
+      const f32x16 acc = linear_mfma_tile(a.mlp_user, a.h0, a.ids, a.num_users, B, a.h0, a.w1,
+                                          2 * a.h0, a.h1, t0, 0, xs, ws, err);
+      const float bn = n < a.h1 ? a.b1[n] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        stage[(wr + mfma32_row(r, h)) * 64 + nc] = n < a.h1 ? acc[r] + bn : 0.f;
+      __syncthreads();
+      // row by row with cert_user_stats' own wave sums (the compiler fuses their first step
+      // into an fma, which the items' butterfly does not reproduce): 16 independent chains
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t b = t0 + r0 + r;
+        if (b < B) {  // uniform
+          // wp * g_u of the row (the one-tile user blocks end before the item blocks: the
+          // gather's latency is not hidden and need not be)
+          const int64_t id = a.ids[b];
+          const bool ok = id >= 0 && id < a.num_users;
+          if (!ok && lane == 0) hnm_flag(err, HNM_ERR_OOB);
+          const float wg = ncf_gather_scale(a.gmf_user, id, a.mf, a.mf, a.wp, kc, ok);
+          const float pv = stage[(r0 + r) * 64 + lane];
+          a.Pu[b * 64 + lane] = pv;
+          a.WGu[b * 64 + lane] = wg;
+          cert_user_stats(vt, fabsf(pv), wg, b, lane, Au, Cu, m0, m1);
+        }
+      }
+      __syncthreads();
     }
   }
-  m0 = wave_max(m0);
-  m1 = wave_max(m1);
-  m2 = wave_max(m2);
-  m3 = wave_max(m3);
-  if (lane == 0) {
-    red[wave][0] = m0;
-    red[wave][1] = m1;
-    red[wave][2] = m2;
-    red[wave][3] = m3;
-  }
-  __syncthreads();
-  if (tid < 4) {
-    float m = red[0][tid];
-    for (int w = 1; w < 4; ++w) m = nmax(m, red[w][tid]);
-    // per-block partials (no same-address atomics); reduced by cert_scales_kernel
-    part[blockIdx.x * 4 + tid] = m;
-  }
+  cert_block_maxima(m0, m1, m2, m3, red, part, items ? blk : item_blocks + blk);
 }
 
 __device__ __forceinline__ float pow2_below_inv(float m) {  // 2^-e with m < 2^e (m > 0)
@@ -1776,11 +1982,22 @@ size_t cert_carve(char* base, int64_t B, int64_t I, int K, int num_cus, int wg, 
   return off;
 }
 
+// Blocks of the statistics launch (item blocks first), whose partials cert_scales_kernel
+// reduces: at most 1,024 + 256, the slots of x.part.  fused: ncf_tables_kernel (64-row tiles).
+struct StatBlocks {
+  int items, users;
+};
+StatBlocks cert_stat_blocks(int64_t B, int64_t I, bool fused) {
+  const int rows = fused ? 64 : 4;
+  return {(int)std::min<int64_t>(1024, hnm_cdiv(I, rows)),
+          (int)std::min<int64_t>(256, hnm_cdiv(B, rows))};
+}
+
 hnm_status cert_prepare(hnm_ctx* ctx, const hnm_ncf_weights* w, const NcfTabs& t, int64_t B,
                         const CertWs& x, const CertDeep* dp) {
   const int64_t I = w->num_items;
-  const int ib = (int)std::min<int64_t>(1024, hnm_cdiv(I, 4));
-  const int ub = (int)std::min<int64_t>(256, hnm_cdiv(B, 4));
+  const StatBlocks sb = cert_stat_blocks(B, I, t.stats);
+  const int ib = sb.items, ub = sb.users;
   // the weights behind layer 2's outputs: wm (two-layer tower) or u = |wp3|^T |W3| (deep)
   const float* wm = w->wp + w->mf;
   const CertDeep dv = dp ? *dp : CertDeep{};
@@ -1789,9 +2006,11 @@ hnm_status cert_prepare(hnm_ctx* ctx, const hnm_ncf_weights* w, const NcfTabs& t
     HNM_LAUNCH_CHECK();
     wm = x.u;
   }
-  hipLaunchKernelGGL(cert_stats_kernel, dim3(ib + ub), dim3(256), 0, ctx->stream, t, B, I, w->mf,
-                     w->w2, w->h1, w->h2, wm, x.prm, x.Au, x.Cu, x.Bi, x.Di, x.part, ib, ub);
-  HNM_LAUNCH_CHECK();
+  if (!t.stats) {  // else ncf_cert_tables left Au, Cu, Bi, Di and the partials with the tables
+    hipLaunchKernelGGL(cert_stats_kernel, dim3(ib + ub), dim3(256), 0, ctx->stream, t, B, I, w->mf,
+                       w->w2, w->h1, w->h2, wm, x.prm, x.Au, x.Cu, x.Bi, x.Di, x.part, ib, ub);
+    HNM_LAUNCH_CHECK();
+  }
   hipLaunchKernelGGL(cert_scales_kernel, dim3(1), dim3(256), 0, ctx->stream, w->w2, w->h1, w->h2,
                      w->b2, wm, w->bp, x.prm, x.part, ib, ub, x.ovf_cnt, dv);
   HNM_LAUNCH_CHECK();
@@ -1835,6 +2054,22 @@ ScanArgs scan_args(const CertWs& x, int64_t B, bool deep) {
 }
 
 }  // namespace
+
+hnm_status ncf_cert_tables(hnm_ctx* ctx, const hnm_ncf_weights* w, const int64_t* ids, int64_t B,
+                           float* Pu, float* WGu, float* Qi, int K, void* scratch, bool strided) {
+  const int64_t I = w->num_items;
+  CertWs x;
+  cert_carve((char*)scratch, B, I, K, ctx->num_cus, ncf_cert_wg(ctx), strided, &x);
+  const StatBlocks sb = cert_stat_blocks(B, I, true);
+  const NcfTablesArgs a{w->mlp_user, w->mlp_item, w->gmf_user, w->w1,  w->b1, w->wp,
+                        w->item_proj, ids,         w->num_users, w->h0, w->h1, w->mf,
+                        Pu,           WGu,         Qi,           w->gmf_item, w->mf};
+  hipLaunchKernelGGL(ncf_tables_kernel, dim3(sb.items + sb.users), dim3(256), 0, ctx->stream, a, B,
+                     I, w->w2, w->h2, w->wp + w->mf, x.Au, x.Cu, x.Bi, x.Di, x.part, sb.items,
+                     sb.users, ctx->err_dev);
+  HNM_LAUNCH_CHECK();
+  return HNM_OK;
+}
 
 bool ncf_cert_eligible(const hnm_ncf_weights* w, int K) {
   // the scan addresses Q16 / G16 by 32-bit element offsets (item * 64 < 2^31: 33.5M items)

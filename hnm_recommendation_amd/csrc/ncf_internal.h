@@ -9,7 +9,16 @@ struct NcfTabs {
   const float* Qi;   // [I, 64]  pair-permuted  W1i m_i
   const float* G;    // [I, ldg] natural order, ldg % 4 == 0, 16-byte aligned, zero-padded
   int64_t ldg;
+  bool stats;        // ncf_cert_tables built the tables: the bound statistics came with them
 };
+
+// Column c of the row wp_gmf * g_u (gather_scale_kernel in ncf.hip, ncf_tables_kernel in
+// ncf_cert.hip): ok = the row's id is in range.
+__device__ __forceinline__ float ncf_gather_scale(const float* __restrict__ tab, int64_t id,
+                                                  int ld, int d, const float* __restrict__ s,
+                                                  int c, bool ok) {
+  return (ok && c < d) ? tab[id * ld + c] * s[c] : 0.f;
+}
 
 // Exact fp32 top-K over all items (ncf32_kernel LIST mode + partition merge) for the
 // request rows rows[0 .. *nrows) (device pointers; rows == nullptr: rows 0 .. B).
@@ -51,6 +60,14 @@ bool ncf_cert_eligible(const hnm_ncf_weights* w, int K);
 // ([B, I / 8] values) is carved only then; begin and finish of one call must agree on it
 size_t ncf_cert_bytes(int64_t B, int64_t I, int K, int num_cus, int wg, bool strided);
 int ncf_cert_wg(const hnm_ctx* ctx);  // scan workgroups per CU of the selected variant
+// The per-call tables and the bound statistics of their rows in one launch (ncf_tables_kernel,
+// HNM_OPT_NCF_TABLES), for a call that goes on to ncf_cert_begin / ncf_cert_debug with the same
+// (K, scratch, strided): P_u, wp * g_u and -- unless w->item_proj is set -- Q_i are written to
+// Pu / WGu / Qi [*, 64], A_u, C_u, B_i, D_i and the maxima's partials into the scratch.  The
+// caller checks the shape: two-layer tower, h1 <= 64, mf <= 64 a multiple of 4, h0 a multiple of
+// 32, 16-B aligned tables.  The NcfTabs passed on carry stats = true.
+hnm_status ncf_cert_tables(hnm_ctx* ctx, const hnm_ncf_weights* w, const int64_t* ids, int64_t B,
+                           float* Pu, float* WGu, float* Qi, int K, void* scratch, bool strided);
 hnm_status ncf_cert_topk(hnm_ctx* ctx, const hnm_ncf_weights* w, const NcfTabs& t, int64_t B,
                          const int64_t* mptr, const int32_t* midx, int K, void* scratch,
                          bool strided, float* ov, int64_t* oi);

@@ -98,6 +98,11 @@ enum { HNM_OPT_PREFILTER = 1,
                                   (default) = the fp32-MFMA kernel where K % 32 == 0 (exact fp32
                                   fma chain in k order: bitwise the VALU kernel); 0 = the VALU
                                   kernel everywhere (the A/B and parity switch) */ };
+/* NeuralCF certified top-K, two-layer towers up to 64 wide with h0 a multiple of 32 and 16-B
+ * aligned tables: 1 (default) = one launch builds the per-call tables (P_u, wp * g_u, Q_i) and
+ * the bound statistics of their rows; 0 = the separate projection, gather and statistics
+ * launches (same tables and results bitwise: the A/B and parity switch) */
+#define HNM_OPT_NCF_TABLES 7
 hnm_status hnm_ctx_set_option(hnm_ctx* ctx, int option, int64_t value);
 /* Pre-filter counters since the last reset (counted only while HNM_OPT_STATS is 1): out[0]
  * rows scored, out[1] candidates re-scored in fp32, out[2] rows that took the exact fallback

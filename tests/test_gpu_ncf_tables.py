@@ -1,0 +1,210 @@
+"""GPU: the one-launch NeuralCF tables (ncf_cert.hip ncf_tables_kernel, HNM_OPT_NCF_TABLES).
+
+With the option at 1 the certified two-layer path builds P_u, wp * g_u, Q_i and the bound
+statistics of their rows (A_u, C_u, B_i, D_i, the six maxima) in one launch; at 0 it runs the
+separate projection, gather and statistics launches.  Every table and
+every bound term is the same arithmetic in the same order, so everything observable must be
+bitwise equal: top-k (scores and items, with and without a history filter), the pre-filter's
+counters, its approximate scores and bounds, the item-sharded protocol -- and equal to the exact
+fp32 scan.  Shapes are the smallest the certified path takes (>= 8,192 items, >= 16 rows): a
+catalogue that is no multiple of 64 or 4, an odd batch with a partial wave, more than one tile
+of users; towers: the default, a padded one (h0 = h1 = 32, mf 16) and one with h0 = 24 that
+keeps the separate launches (the k-loop needs h0 % 32 == 0).
+
+The library does not expose the per-call Q table, so "hnm_ncf_item_proj_f32 equals the Q the
+kernel writes" is checked through everything that reads Q: with cache_item_tables() on the
+kernel reads the projection hnm_ncf_item_proj_f32 built, off it reads its own, and the f16 scan
+(approx, bound), the fp32 re-scoring and the exact fallback over the whole catalogue (the
+`huge` weights put every row on it, k = 64) must agree bit for bit."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from hnm_recommendation_amd import NeuralCF, _lib
+from hnm_recommendation_amd import sharding as S
+from hnm_recommendation_amd import synthetic as syn
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+U, K = 3001, 12
+OPT = _lib.HNM_OPT_NCF_TABLES
+
+TOWERS = {
+    "default": dict(mf_dim=64, mlp_dims=[128, 64, 32]),
+    "mf16": dict(mf_dim=16, mlp_dims=[64, 32, 16]),   # h0 = 32, h1 = 32: padded rows
+    "h24": dict(mf_dim=16, mlp_dims=[48, 32, 16]),    # h0 = 24: the separate launches
+}
+WEIGHTS = ["init", "norms", "student_t", "huge"]
+SHAPES = [(8229, 37), (8256, 128)]
+
+
+@functools.lru_cache(maxsize=None)
+def _state(tower, weights, I):
+    t = TOWERS[tower]
+    sd = syn.ncf_state_dict(U, I, t["mf_dim"], tuple(t["mlp_dims"]), seed=21, bias_scale=0.05)
+    if weights != "init":
+        sd = syn.stress_state_dict(sd, weights, syn.NCF_EMB_KEYS, "mlp_item_embedding.weight", 3)
+    return sd
+
+
+def model(tower, weights, I):
+    m = NeuralCF(U, I, **TOWERS[tower])
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in _state(tower, weights, I).items()})
+    return m.to(DEV).eval()
+
+
+def prefilter_debug(m, users):
+    w, keep = m._weights()
+    B, I = users.numel(), m.num_items
+    approx = torch.empty(B, I, device=DEV)
+    bound = torch.empty(B, I, device=DEV)
+    _lib.check(_lib.fn("hnm_ncf_prefilter_debug_f32")(_lib.ctx(users.device), w, _lib.ptr(users),
+                                                      B, _lib.ptr(approx), I, _lib.ptr(bound)),
+               "hnm_ncf_prefilter_debug_f32")
+    _lib.sync_check(users.device)
+    return approx, bound
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32).cpu().numpy()
+
+
+def history(users, I, seed=0):
+    rng = np.random.default_rng(seed)
+    return {int(u): set(rng.integers(0, I, 40).tolist()) for u in users.cpu().numpy()[::2]}
+
+
+def observe(m, users, filt, k=K, debug=True):
+    """Everything the certified path shows: top-k without / with the filter (score bits, items),
+    the counters of both calls, and the f16 scan's approximate scores and bounds."""
+    dev = users.device
+    out = {}
+    _lib.prefilter_stats(dev, reset=True)
+    _lib.set_option(dev, _lib.HNM_OPT_STATS, 1)
+    try:
+        for name, f in (("plain", None), ("filtered", filt)):
+            v, i = m.recommend_with_scores(users, filter_items=f, k=k)
+            out[name + ".scores"], out[name + ".items"] = bits(v), i.cpu().numpy()
+            out[name + ".stats"] = np.asarray(_lib.prefilter_stats(dev, reset=True))
+    finally:
+        _lib.set_option(dev, _lib.HNM_OPT_STATS, 0)
+    if debug:
+        approx, bound = prefilter_debug(m, users)
+        out["approx"], out["bound"] = bits(approx), bits(bound)
+    return out
+
+
+def assert_same(a, b, what):
+    assert a.keys() == b.keys()
+    for key in a:
+        assert np.array_equal(a[key], b[key]), f"{what}: {key} differs"
+
+
+@pytest.fixture(autouse=True)
+def _restore_options():
+    yield
+    _lib.set_option(torch.device(DEV, 0), OPT, 1)
+    _lib.set_prefilter(torch.device(DEV, 0), True)
+
+
+CASES = [(t, w, s) for t in TOWERS for w in WEIGHTS for s in SHAPES]
+CASES += [("default", "init", (8229, 128)), ("default", "init", (8256, 37))]
+
+
+@pytest.mark.parametrize("tower,weights,shape", CASES)
+def test_tables_option_bitwise(tower, weights, shape):
+    I, B = shape
+    m = model(tower, weights, I)
+    users = torch.from_numpy(syn.user_batch(U, B, seed=B)).to(DEV)
+    dev = users.device
+    filt = history(users, I)
+    k = 64 if weights == "huge" else K   # every row on the exact fallback: more of Q is seen
+    got = {}
+    for v in (1, 0):
+        _lib.set_option(dev, OPT, v)
+        got[v] = observe(m, users, filt, k)
+    assert_same(got[1], got[0], "option 1 vs 0")
+    rows, cands, fallback = got[1]["plain.stats"][:3]
+    assert rows == B
+    if weights == "huge":
+        assert fallback == B  # |Q| above 2^40: the bound is unusable
+    # option 1 against the exact fp32 scan of every item
+    _lib.set_option(dev, OPT, 1)
+    _lib.set_prefilter(dev, False)
+    try:
+        for name, f in (("plain", None), ("filtered", filt)):
+            v, i = m.recommend_with_scores(users, filter_items=f, k=k)
+            assert np.array_equal(i.cpu().numpy(), got[1][name + ".items"]), name
+            assert np.array_equal(bits(v), got[1][name + ".scores"]), name
+    finally:
+        _lib.set_prefilter(dev, True)
+    # the cached projection (hnm_ncf_item_proj_f32) in place of the Q the kernel writes
+    m.cache_item_tables(True)
+    try:
+        cached = observe(m, users, filt, k)
+        assert m._item_proj is not None
+    finally:
+        m.cache_item_tables(False)
+    assert_same(cached, got[1], "cache_item_tables")
+
+
+@pytest.mark.parametrize("tower", ["default", "mf16"])
+def test_tables_two_shards(tower):
+    """Begin and finish of the item-sharded protocol (sharding.ncf_shard_topk, two emulated
+    shards of >= 8,192 items each, the bound lists merged as tests/test_gpu_sharding.py does):
+    the same lists, the same bound and the same merged top-k under either option, equal to the
+    unsharded top-k."""
+    I, B, G = 16_459, 37, 2
+    m = model(tower, "init", I)
+    users = torch.from_numpy(syn.user_batch(U, B, seed=4)).to(DEV)
+    dev = users.device
+    res = {}
+    for v in (1, 0):
+        _lib.set_option(dev, OPT, v)
+        shards = [S.ncf_shard_topk(m, *S.shard_range(I, r, G), K) for r in range(G)]
+        lists, singles = [], []
+        for s in shards:
+            lists.append(s.begin_lists(users))
+            s.abort()
+            singles.append(s.begin(users))
+            s.abort()
+        assert all(torch.isfinite(x).all() for x in lists)  # both shards are certified
+        merged = torch.topk(torch.cat(lists, dim=1), K, dim=1).values[:, K - 1].contiguous()
+        vs, ids = [], []
+        for r, s in enumerate(shards):
+            s.begin_lists(users)
+            val, idx = s.finish(users, merged)
+            lo = S.shard_range(I, r, G)[0]
+            vs.append(val)
+            ids.append(torch.where(idx >= 0, idx + lo, idx))
+        gv, gi = S.hip_merge(torch.stack(vs), torch.stack(ids), K)
+        res[v] = {"lists": bits(torch.stack(lists)), "single": bits(torch.stack(singles)),
+                  "parts.v": bits(torch.stack(vs)), "parts.i": torch.stack(ids).cpu().numpy(),
+                  "scores": bits(gv), "items": gi.cpu().numpy()}
+    assert_same(res[1], res[0], "shards, option 1 vs 0")
+    _lib.set_option(dev, OPT, 1)
+    v1, i1 = m.recommend_with_scores(users, k=K)
+    assert np.array_equal(res[1]["items"], i1.cpu().numpy())
+    assert np.array_equal(res[1]["scores"], bits(v1))
+
+
+@pytest.mark.parametrize("opt", [1, 0])
+def test_tables_device_id_out_of_range(opt):
+    """A device-side id outside [0, U) is flagged by the table kernel as by the separate
+    launches: IndexError after the call, and the next call is clean."""
+    I, B = 8229, 37
+    m = model("default", "init", I)
+    users = torch.from_numpy(syn.user_batch(U, B, seed=8)).to(DEV)
+    dev = users.device
+    _lib.set_option(dev, OPT, opt)
+    bad = users.clone()
+    bad[B - 2] = U
+    with pytest.raises(IndexError):
+        m.recommend_with_scores(bad, k=K)
+    bad[B - 2] = -1
+    with pytest.raises(IndexError):
+        m.recommend_with_scores(bad, k=K)
+    v, i = m.recommend_with_scores(users, k=K)
+    assert torch.isfinite(v).all() and (i >= 0).all()
