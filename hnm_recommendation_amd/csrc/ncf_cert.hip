@@ -29,6 +29,13 @@
 // below u.  Hence |err| <= 5.1u (c0 + A_u + B_i) + 2.1u C_u D_i + (subnormal terms) and
 // we use e(u, i) = 6u (c0 + A_u + B_i + C_u D_i) + abs_slack.
 // tests/test_gpu_prefilter.py checks (*) pair by pair on the full catalogue.
+// The accumulation slack holds for any summation order: the f16 x f16 products are exact in the
+// fp32 accumulator and a score is at most 96 fp32 additions (64 layer-2 terms or 64 GMF terms,
+// then 32 units) however the matrix instructions group them.  So both layouts of the scan
+// (HNM_OPT_SCAN_SHAPE: 1 = layer 2 and the GMF on v_mfma_f32_16x16x32_f16, the default; 0 = on
+// v_mfma_f32_32x32x16_f16; the A/B and parity switch) satisfy (*) with the same e(u, i); their
+// approximate scores may differ in the last bits, the returned top-K never does
+// (tests/test_gpu_ncf_scan_shape.py).
 //
 // Scaling: every f16 operand is scaled by a power of two so its magnitude is <= 1 (layer-1
 // inputs <= 0.5, which also makes the packed add's [0,1] CLAMP an exact ReLU:
@@ -765,13 +772,30 @@ __device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
 // units, columns = items) and whose A row idx = 2 user + g holds wp3: four of them chained on the
 // folded seeds leave the test values where the two-layer epilogue leaves them.  DEBUG uses the
 // same matrix epilogue (seeds = GMF only).  Two waves per SIMD (28 more live registers).
-template <int MODE, bool DEEP = false>
+// SHAPE 1 (HNM_OPT_SCAN_SHAPE, two-layer towers): layer 2 and the GMF on v_mfma_f32_16x16x32_f16,
+// everything outside the pair body as it is.  Per user 2 unit halves m x 2 item halves n x 2
+// k-steps s (8 x 16 cycles, the 4 x 32 of the other shape); the B operand clamp(P~ + Q~) of (n, s)
+// serves both m, and the lane's P~ fragment depends on (s, k-group) only, so a user takes 2
+// ds_read_b128 of P~ a tile instead of 4.  The four f32x4 accumulators of a user are seeded with
+// b2 (8 registers).  Epilogue: the converted accumulators m = 0, 1 of (user, n) are one B operand
+// of a 16x16x32 whose A row 2 user + n holds wm in that k order -- the same 4 chained MFMAs on
+// the folded seeds, the same output lanes, ballots and appends.  The GMF is 2 x 2 x 2 of the same
+// instruction (users as rows) stored into the same g7 table.  Its DEBUG pass takes this matrix
+// epilogue with GMF-only seeds and the deep DEBUG pass's dense store.  The tiles' rows are 128 B
+// with XOR-swizzled 16-B chunks (conflict-free for this shape's b128 reads: see so0 / so1).
+// 164 VGPRs, no scratch (SHAPE 0: 168 and one spilled register); three waves per SIMD.
+template <int MODE, bool DEEP = false, int SHAPE = 0>
 __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kernel(ScanArgs A) {
-  constexpr int RS = 72;   // LDS row stride in halfs (144 B): conflict-free b128 reads
+  constexpr bool S16 = SHAPE == 1;  // layer 2 and the GMF on v_mfma_f32_16x16x32_f16
+  static_assert(!(S16 && DEEP), "the deep scan has the 32x32x16 layout only");
+  // LDS row stride in halfs: 144 B (conflict-free b128 reads of the 32x32x16 operands: lane
+  // (j, h) reads row j) / S16: 128 B with the row's 16-B chunks XOR-swizzled (s16_chunk)
+  constexpr int RS = S16 ? 64 : 72;
   constexpr int NU = 128;  // users per workgroup
   // the matrix-pipe epilogue and its folded seed table (FOLD: GMF + bound - threshold; the deep
-  // DEBUG pass: GMF alone)
-  constexpr bool FOLD = MODE == SCAN_THRESH || MODE == SCAN_SAMPLE || (DEEP && MODE == SCAN_DEBUG);
+  // and the S16 DEBUG pass: GMF alone)
+  constexpr bool FOLD = MODE == SCAN_THRESH || MODE == SCAN_SAMPLE ||
+                        ((DEEP || S16) && MODE == SCAN_DEBUG);
   if (MODE == SCAN_SAMPLE && A.gate && *A.gate == 0) return;  // whole grid: gated off
   __shared__ __attribute__((aligned(16))) _Float16 qs[2][TILE * RS];  // double-buffered tiles
   __shared__ __attribute__((aligned(16))) _Float16 gs[2][TILE * RS];
@@ -799,18 +823,40 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
     if (ublk + r < A.B) v = *reinterpret_cast<const h8*>(A.P16 + (ublk + r) * 64 + 8 * c);
     *reinterpret_cast<h8*>(&ps[r * 64 + 8 * c]) = v;
   }
+  // S16 (16x16x32: lane holds A[row lane & 15][k = 8 (lane >> 4) + e], B[k][col lane & 15] and
+  // D[row 4 (lane >> 4) + r][col lane & 15]): aw[2 m + s] = W2~ rows 16 m + c16, k-step s;
+  // ag[2 m + s] = the users 16 m + c16 of the wave; b2q[m] = the seeds of units 16 m + 4 g4 + r
+  const int c16 = lane & 15, g4 = lane >> 4;
   h8 aw[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) aw[s] = *reinterpret_cast<const h8*>(A.W2h + j * 64 + 16 * s + 8 * h);
   h8 ag[4];  // GMF A operand: this wave's users' wp*g_u rows
+  f32x16 b2c = {};
+  f32x4 b2q[2];
+  if constexpr (S16) {
 #pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    h8 z = {};
-    ag[s] = j < nu ? *reinterpret_cast<const h8*>(A.WG16 + (u0 + j) * 64 + 16 * s + 8 * h) : z;
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int ur = 16 * m + c16;
+        h8 z = {};
+        aw[2 * m + s] = *reinterpret_cast<const h8*>(A.W2h + ur * 64 + 32 * s + 8 * g4);
+        ag[2 * m + s] =
+            ur < nu ? *reinterpret_cast<const h8*>(A.WG16 + (u0 + ur) * 64 + 32 * s + 8 * g4) : z;
+      }
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) b2q[m][r] = A.b2s[16 * m + 4 * g4 + r];
+  } else {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) aw[s] = *reinterpret_cast<const h8*>(A.W2h + j * 64 + 16 * s + 8 * h);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      h8 z = {};
+      ag[s] = j < nu ? *reinterpret_cast<const h8*>(A.WG16 + (u0 + j) * 64 + 16 * s + 8 * h) : z;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) b2c[r] = A.b2s[mfma32_row(r, h)];
   }
-  f32x16 b2c;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) b2c[r] = A.b2s[mfma32_row(r, h)];
   // epilogue A operands (16x16x32: lane holds A[row lane & 15][k = 8 (lane >> 4) + e])
   h8 ewa[2], ewb[2];
   h2 wm2[8];  // DEBUG: wm of this lane's accumulator rows, in pairs
@@ -832,6 +878,18 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
       for (int e = 0; e < 4; ++e) ep[idx][e] = m == idx ? A.wph[4 * kg + e] : (_Float16)0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) b3c[r] = A.b3s[4 * kg + r];
+  } else if constexpr (S16) {
+    // the B operand of (user, item half n) is the lane's converted accumulators m = 0, 1 as one
+    // h8: k = 8 g4 + e is unit 16 (e >> 2) + 4 g4 + (e & 3); A row 2 user + n holds wm in that
+    // order (ewa[n]: user a, ewb[n]: user b), every k-group of the item half's own
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const _Float16 wv = A.wmh[16 * (e >> 2) + 4 * g4 + (e & 3)];
+        ewa[n][e] = c16 == n ? wv : (_Float16)0.f;
+        ewb[n][e] = c16 == 2 + n ? wv : (_Float16)0.f;
+      }
   } else {
     const int erow = lane & 15, eg = lane >> 4;
 #pragma unroll
@@ -918,8 +976,10 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
   };
   auto stash = [&](int buf) {
     const int srow = srow_of(), sc = sc_of();
-    *reinterpret_cast<h8*>(&qs[buf][srow * RS + 8 * sc]) = nq;
-    *reinterpret_cast<h8*>(&gs[buf][srow * RS + 8 * sc]) = ng;
+    // S16: chunk sc of row r lies at chunk position sc ^ (r >> 1 & 7) (the read side: s16 below)
+    const int pc = S16 ? sc ^ ((srow >> 1) & 7) : sc;
+    *reinterpret_cast<h8*>(&qs[buf][srow * RS + 8 * pc]) = nq;
+    *reinterpret_cast<h8*>(&gs[buf][srow * RS + 8 * pc]) = ng;
   };
   int64_t t = 0;
   if (t < ntiles) {
@@ -941,8 +1001,56 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
     int lrow;  // lane (j, h)'s operand row offset in the tile buffers (recomputed: see srow_of)
     asm volatile("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(lrow) : "v"(j), "v"(RS), "v"(8 * h));
 
+    // S16: lane (c16, g4)'s operand offsets in the tile buffers at k-steps 0 and 1, item half 0
+    // (half n: + 16 n RS).  Row r keeps chunk x at position x ^ (r >> 1 & 7): a b128 read's
+    // 16-lane groups pair eight lanes of one k-group with eight of the next, whose chunks differ
+    // in bit 0, and the rows' swizzles (0, 1, 6, 7 against 2, 3, 4, 5 on either row parity) keep
+    // the sixteen 16-B slots of the 256-B bank row distinct.  Recomputed per tile as lrow is.
+    int so0 = 0, so1 = 0;
+    if constexpr (S16) {
+      int ln;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+      const int x0 = (ln >> 4) ^ ((ln >> 1) & 7);
+      so0 = (ln & 15) * RS + 8 * x0;
+      so1 = (ln & 15) * RS + 8 * (x0 ^ 4);
+    }
+
     if (nu > 0) {
-    {  // GMF of the wave's 32 users x 32 items, in score units
+    if constexpr (S16) {  // GMF as 2 x 2 x 2 16x16x32: users 16 m + c16 x items c16 + 16 n
+      f32x4 ga[2][2] = {};
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          const h8 gb = *reinterpret_cast<const h8*>(&gs[cur][(s ? so1 : so0) + 16 * n * RS]);
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+            ga[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ag[2 * m + s], gb, ga[m][n], 0, 0, 0);
+        }
+      // the same folded table as below: lane (c16, g4) holds users 16 m + 4 g4 + r of items
+      // c16 + 16 n, whose bound terms lanes c16 + 16 n carry
+      constexpr float sgn = MODE == SCAN_THRESH ? 1.f : -1.f;
+      float bjn[2] = {0.f, 0.f}, djn[2] = {0.f, 0.f};
+      if (MODE != SCAN_DEBUG) {
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          bjn[n] = __shfl(bj, c16 + 16 * n);
+          djn[n] = __shfl(dj, c16 + 16 * n);
+        }
+      }
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * m + 4 * g4 + r;
+          const float2 tc = ut[wave][row];
+#pragma unroll
+          for (int n = 0; n < 2; ++n)
+            g7[(((row >> 1) * 16 + c16) << 2) + ((row & 1) << 1) + n] =
+                MODE == SCAN_DEBUG ? ga[m][n][r] * cg
+                                   : (ga[m][n][r] * cg + sgn * fmaf(tc.y, djn[n], bjn[n])) - tc.x;
+        }
+    } else {  // GMF of the wave's 32 users x 32 items, in score units
       f32x16 gacc = {};
 #pragma unroll
       for (int s = 0; s < 4; ++s)
@@ -965,9 +1073,11 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         for (int r = 0; r < 16; ++r) gsm[wave][mfma32_row(r, h)][j] = gacc[r] * cg;
       }
     }
-    h8 q[4];
+    h8 q[4];  // S16: q[2 n + s] = Q~[item c16 + 16 n][k = 32 s + 8 g4 + e]
 #pragma unroll
-    for (int s = 0; s < 4; ++s) q[s] = *reinterpret_cast<const h8*>(&qs[cur][lrow + 16 * s]);
+    for (int s = 0; s < 4; ++s)
+      q[s] = *reinterpret_cast<const h8*>(
+          S16 ? &qs[cur][((s & 1) ? so1 : so0) + 16 * (s >> 1) * RS] : &qs[cur][lrow + 16 * s]);
     const int64_t n = base + j;
     const int64_t tile_end = std::min<int64_t>(base + TILE, part_end);
     const int nv = (int)(tile_end - base);  // valid items of the tile
@@ -990,13 +1100,39 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
       }
     }
 
-    const _Float16* pw = &ps[(wave * upw) * 64 + 8 * h];  // user r, k-step s: pw[r * 64 + 16 s]
+    // user r, k-step s: pw[r * 64 + 16 s] (S16: pw[r * 64 + 32 s], the lane's k-group g4 -- one
+    // fragment serves both item halves)
+    const _Float16* pw = &ps[(wave * upw) * 64 + 8 * (S16 ? g4 : h)];
     for (int u = 0; u < nu; u += 2) {
       // user b = u + 1 even past nu (zero P~ rows; FOLD: folded term -inf / not stored)
       const int ua = u, ub = u + 1;
       const bool hasb = ub < nu;
       const int uh = h ? ub : ua;
       f32x16 acc0 = b2c, acc1 = b2c;
+      f32x4 ca[2][2], cb[2][2];  // S16: [unit half m][item half n], users a and b
+      if constexpr (S16) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int n = 0; n < 2; ++n) ca[m][n] = cb[m][n] = b2q[m];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const h8 pa = *reinterpret_cast<const h8*>(&pw[ua * 64 + 32 * s]);
+          const h8 pb = *reinterpret_cast<const h8*>(&pw[ub * 64 + 32 * s]);
+#pragma unroll
+          for (int n = 0; n < 2; ++n) {
+            h8 x = pa + q[2 * n + s];
+            x = __builtin_elementwise_min(__builtin_elementwise_max(x, (h8){}), (h8)(_Float16)1.f);
+            h8 y = pb + q[2 * n + s];
+            y = __builtin_elementwise_min(__builtin_elementwise_max(y, (h8){}), (h8)(_Float16)1.f);
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+              ca[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aw[2 * m + s], x, ca[m][n], 0, 0, 0);
+              cb[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aw[2 * m + s], y, cb[m][n], 0, 0, 0);
+            }
+          }
+        }
+      } else {
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         // each fragment is read right before its MFMA (fewer live registers than a prefetch)
@@ -1009,14 +1145,22 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         acc0 = mfma16(aw[s], x, acc0);
         acc1 = mfma16(aw[s], y, acc1);
       }
+      }  // !S16
       if constexpr (FOLD) {
-        h8 ya[2], yb[2];
+        h8 ya[2], yb[2];  // S16: [item half n], the accumulators m = 0, 1 of the half as one h8
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          ya[0][e] = (_Float16)acc0[e];
-          ya[1][e] = (_Float16)acc0[8 + e];
-          yb[0][e] = (_Float16)acc1[e];
-          yb[1][e] = (_Float16)acc1[8 + e];
+          if constexpr (S16) {
+            ya[0][e] = (_Float16)ca[e >> 2][0][e & 3];
+            ya[1][e] = (_Float16)ca[e >> 2][1][e & 3];
+            yb[0][e] = (_Float16)cb[e >> 2][0][e & 3];
+            yb[1][e] = (_Float16)cb[e >> 2][1][e & 3];
+          } else {
+            ya[0][e] = (_Float16)acc0[e];
+            ya[1][e] = (_Float16)acc0[8 + e];
+            yb[0][e] = (_Float16)acc1[e];
+            yb[1][e] = (_Float16)acc1[8 + e];
+          }
         }
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
@@ -2024,10 +2168,14 @@ hnm_status cert_prepare(hnm_ctx* ctx, const hnm_ncf_weights* w, const NcfTabs& t
 
 template <int MODE>
 void launch_scan(hnm_ctx* ctx, dim3 grid, const ScanArgs& a) {
+  // HNM_OPT_SCAN_SHAPE picks the two-layer scan's layout, every pass of a call alike (the deep
+  // scan has the 32x32x16 layout only)
   if (a.W3h)
     hipLaunchKernelGGL((ncf16_scan_kernel<MODE, true>), grid, dim3(256), 0, ctx->stream, a);
+  else if (ctx->scan_shape)
+    hipLaunchKernelGGL((ncf16_scan_kernel<MODE, false, 1>), grid, dim3(256), 0, ctx->stream, a);
   else
-    hipLaunchKernelGGL((ncf16_scan_kernel<MODE, false>), grid, dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL((ncf16_scan_kernel<MODE, false, 0>), grid, dim3(256), 0, ctx->stream, a);
 }
 
 ScanArgs scan_args(const CertWs& x, int64_t B, bool deep) {

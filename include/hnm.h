@@ -103,6 +103,11 @@ enum { HNM_OPT_PREFILTER = 1,
  * the bound statistics of their rows; 0 = the separate projection, gather and statistics
  * launches (same tables and results bitwise: the A/B and parity switch) */
 #define HNM_OPT_NCF_TABLES 7
+/* NeuralCF certified top-K, two-layer towers: the f16 scan's layer 2 and GMF on
+ * v_mfma_f32_16x16x32_f16 (1, default) or on v_mfma_f32_32x32x16_f16 (0).  Both layouts satisfy
+ * the same certified bound, so every returned id and score is bitwise the same (the A/B and
+ * parity switch); the deep towers' scan ignores it. */
+#define HNM_OPT_SCAN_SHAPE 8
 hnm_status hnm_ctx_set_option(hnm_ctx* ctx, int option, int64_t value);
 /* Pre-filter counters since the last reset (counted only while HNM_OPT_STATS is 1): out[0]
  * rows scored, out[1] candidates re-scored in fp32, out[2] rows that took the exact fallback

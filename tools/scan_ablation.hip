@@ -1,10 +1,12 @@
 // Timing harness of ncf16_scan_kernel (THRESH mode, no appends) at the bench shape
 // (B = 4096 users x 105,542 items, 24 partitions): kernel-only time, best of 7 after a
-// clock warm-up, so scan variants can be compared without the rest of the step.
+// clock warm-up, so scan variants can be compared without the rest of the step.  Both layouts
+// of the two-layer scan are timed, alternating (SHAPE 0: 32x32x16, 1: 16x16x32;
+// HNM_OPT_SCAN_SHAPE).
 // Diagnostic build only:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -c tools/scan_ablation.hip -o build/scan_ablation.o
-//   hipcc --offload-arch=gfx950 build/scan_ablation.o build/obj/{api,score,ncf,graph,widedeep}.o \
-//         -o build/scan_ablation
+//   hipcc --offload-arch=gfx950 build/scan_ablation.o <every build/obj/*.o but ncf_cert.o> \
+//         -L/opt/rocm/lib -lrccl -o tools/bin/scan_ablation
 #include "../hnm_recommendation_amd/csrc/ncf_cert.hip"
 
 #include <vector>
@@ -23,6 +25,7 @@ static T* dev_fill(size_t n, float lo, float hi, unsigned seed) {
   return d;
 }
 
+template <int SHAPE>
 static float time_scan(dim3 grid, const ScanArgs& a) {
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0);
@@ -30,7 +33,7 @@ static float time_scan(dim3 grid, const ScanArgs& a) {
   float best = 1e30f;
   for (int rep = 0; rep < 8; ++rep) {
     (void)hipEventRecord(e0);
-    hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH>), grid, dim3(256), 0, 0, a);
+    hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, SHAPE>), grid, dim3(256), 0, 0, a);
     (void)hipEventRecord(e1);
     (void)hipEventSynchronize(e1);
     if (hipGetLastError() != hipSuccess) printf("launch error\n");
@@ -65,6 +68,7 @@ int main() {
   a.prm = prm;
   a.B = B;
   a.I = I;
+  a.upw = 32;
 
   a.ipp = sh.part.ipp;
   a.NP = sh.part.np;
@@ -77,10 +81,11 @@ int main() {
   for (int w = 0; w < 100; ++w)  // clock warm-up (~0.2 s of scan work)
     hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH>), grid, dim3(256), 0, 0, a);
   (void)hipDeviceSynchronize();
-  for (int rep = 0; rep < 3; ++rep) {
-    const float ms = time_scan(grid, a);
-    printf("ncf16_scan  %7.3f ms  %6.1f TF useful  %5.2f cyc/user-tile/SIMD @2.2GHz\n", ms,
-           useful / (ms * 1e-3) / 1e12, ms * 1e-3 * 2.2e9 / (pairs / 32 / 1024));
+  for (int rep = 0; rep < 6; ++rep) {
+    const int shape = rep & 1;
+    const float ms = shape ? time_scan<1>(grid, a) : time_scan<0>(grid, a);
+    printf("ncf16_scan shape %d  %7.3f ms  %6.1f TF useful  %5.2f cyc/user-tile/SIMD @2.2GHz\n",
+           shape, ms, useful / (ms * 1e-3) / 1e12, ms * 1e-3 * 2.2e9 / (pairs / 32 / 1024));
   }
   return 0;
 }
