@@ -29,8 +29,6 @@
 #include "hnm_device.h"
 #include "sample_kth.h"
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int64_t DCERT_MIN_ITEMS = 8192;
@@ -76,17 +74,6 @@ struct DParams {
   int bad;
 };
 
-__device__ __forceinline__ float nmax(float a, float b) { return (b > a || b != b) ? b : a; }
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x = nmax(x, __shfl_xor(x, o));
-  return x;
-}
 __device__ __forceinline__ float pow2_below_inv(float m) {  // 2^-e with m < 2^e (m > 0)
   int e;
   (void)frexpf(m, &e);

@@ -15,8 +15,25 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 #define HNM_SENTINEL_IDX 0x7fffffff
+
+// NaN-propagating maximum (a NaN operand wins) and the wave reductions of the certified paths'
+// bound statistics (ncf_cert_params.hip, dot_cert.hip): xor 32, 16, ..., 1 pairing.
+__device__ __forceinline__ float nmax(float a, float b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) x = nmax(x, __shfl_xor(x, o));
+  return x;
+}
 
 __device__ __forceinline__ bool hnm_better(float va, int ia, float vb, int ib) {
   return va > vb || (va == vb && ia < ib);

@@ -1,5 +1,5 @@
 // The k-loop of the fp32-MFMA projection (api.hip linear_rows_mfma_kernel), shared with the
-// NeuralCF table kernel (ncf_cert.hip ncf_tables_kernel): one definition, so the rows either
+// NeuralCF table kernel (ncf_cert_params.hip ncf_tables_kernel): one definition, so the rows either
 // kernel writes are bitwise the same.
 #pragma once
 #include "hnm_device.h"

@@ -719,8 +719,7 @@ static hnm_status ncf_common(hnm_ctx* ctx, const hnm_ncf_weights* w, const int64
   const Partition part = choose_partition(I, ublocks, ctx->num_cus);
   const size_t szC = DENSE ? 0 : hnm_align((size_t)B * part.np * K * 4);
   const bool strided = ctx->strided != 0;
-  const size_t extra =
-      cert ? ncf_cert_bytes(B, I, K, ctx->num_cus, ncf_cert_wg(ctx), strided) : 2 * szC;
+  const size_t extra = cert ? ncf_cert_bytes(ctx, B, I, K, strided) : 2 * szC;
   NcfCall c;
   const NcfCertUse use{K, strided};
   st = ncf_tables(ctx, w, ids, B, extra, &c, true, cert ? &use : nullptr);
@@ -798,9 +797,8 @@ static hnm_status ncf_topk_begin(hnm_ctx* ctx, const hnm_ncf_weights* w, const i
   if (cert) {
     NcfCall c;
     const NcfCertUse use{k, strided};
-    st = ncf_tables(ctx, w, user_ids, B,
-                    ncf_cert_bytes(B, w->num_items, k, ctx->num_cus, ncf_cert_wg(ctx), strided),
-                    &c, true, &use);
+    st = ncf_tables(ctx, w, user_ids, B, ncf_cert_bytes(ctx, B, w->num_items, k, strided), &c,
+                    true, &use);
     if (st) return st;
     st = ncf_cert_begin(ctx, w, c.t, B, mask_ptr, mask_idx, k, c.extra, strided, lower_bound,
                         lists);
@@ -853,9 +851,8 @@ extern "C" hnm_status hnm_ncf_topk_finish_f32(hnm_ctx* ctx, const hnm_ncf_weight
   HNM_REQUIRE(lower_bound, HNM_EINVAL, "ncf_topk_finish: lower_bound is NULL");
   const bool strided = (ctx->pend.flags & HNM_PEND_STRIDED) != 0;  // the begin's layout
   NcfCall c;
-  hnm_status st = ncf_tables(
-      ctx, w, user_ids, B,
-      ncf_cert_bytes(B, w->num_items, k, ctx->num_cus, ncf_cert_wg(ctx), strided), &c, false);
+  hnm_status st = ncf_tables(ctx, w, user_ids, B,
+                             ncf_cert_bytes(ctx, B, w->num_items, k, strided), &c, false);
   if (st) return st;
   return ncf_cert_finish(ctx, w, c.t, B, mask_ptr, mask_idx, k, c.extra, strided, lower_bound,
                          short_ok, out_val, out_idx);
@@ -895,9 +892,8 @@ extern "C" hnm_status hnm_ncf_prefilter_debug_f32(hnm_ctx* ctx, const hnm_ncf_we
   if (B <= 0) return HNM_OK;
   NcfCall c;
   const NcfCertUse use{1, false};
-  st = ncf_tables(ctx, w, user_ids, B,
-                  ncf_cert_bytes(B, w->num_items, 1, ctx->num_cus, ncf_cert_wg(ctx), false), &c,
-                  true, &use);
+  st = ncf_tables(ctx, w, user_ids, B, ncf_cert_bytes(ctx, B, w->num_items, 1, false), &c, true,
+                  &use);
   if (st) return st;
   return ncf_cert_debug(ctx, w, c.t, B, c.extra, approx, lda, bound);
 }
@@ -946,8 +942,8 @@ hnm_status ncf_deep_cert(hnm_ctx* ctx, const hnm_ncf_deep_weights* dw, const int
   CertDeep dp;
   deep_view(dw, ids, &w, &dp);
   NcfCall c;
-  hnm_status st = ncf_tables(
-      ctx, &w, ids, B, ncf_cert_bytes(B, w.num_items, K, ctx->num_cus, ncf_cert_wg(ctx), false), &c);
+  hnm_status st =
+      ncf_tables(ctx, &w, ids, B, ncf_cert_bytes(ctx, B, w.num_items, K, false), &c);
   if (st) return st;
   return ncf_deep_cert_topk(ctx, &w, dp, c.t, B, mptr, midx, K, c.extra, ov, oi, ovf_rows, ovf_cnt,
                             pruned);
@@ -959,8 +955,8 @@ hnm_status ncf_deep_cert_debug(hnm_ctx* ctx, const hnm_ncf_deep_weights* dw, con
   CertDeep dp;
   deep_view(dw, ids, &w, &dp);
   NcfCall c;
-  hnm_status st = ncf_tables(
-      ctx, &w, ids, B, ncf_cert_bytes(B, w.num_items, 1, ctx->num_cus, ncf_cert_wg(ctx), false), &c);
+  hnm_status st =
+      ncf_tables(ctx, &w, ids, B, ncf_cert_bytes(ctx, B, w.num_items, 1, false), &c);
   if (st) return st;
   return ncf_cert_debug(ctx, &w, c.t, B, c.extra, approx, lda, bound, &dp);
 }

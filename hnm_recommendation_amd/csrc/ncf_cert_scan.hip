@@ -1,0 +1,573 @@
+// Certified NeuralCF path, the f16 scan: ncf16_scan_kernel in its three modes (ScanArgs and the
+// modes: ncf_cert_internal.h) x {deep, 32x32x16, 16x16x32} and their launcher.  What the scan
+// computes and why pruning by it is safe: the header of ncf_cert.hip.
+#include <algorithm>
+
+#include "ncf_cert_internal.h"
+
+namespace {
+
+__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+
+// A wave owns 32 users, a workgroup 128; 32-item tiles of Q16/G16 go through LDS.
+// Per (user pair, tile): layer 2 as 4 + 4 v_mfma_f32_32x32x16_f16 (two independent chains;
+// A = W2~, B = clamp(P~ + Q~) built with 16 packed adds per user; v_mfma_f32_32x32x16_f16 B
+// operand: lane (j, h) holds B[k = 8h + e][col j], e = 0..7), GMF once per tile for all 32
+// users (4 MFMAs).  THRESH / SAMPLE: the epilogue wm . relu(H~) of BOTH users runs on the matrix
+// pipe as 4 v_mfma_f32_16x16x32_f16 -- relu(H~) by the [0, 1] clamp of the f32 -> f16
+// converts, the 16x16x32 B operand taking each lane's 8 converted accumulator rows as they lie
+// (k-group g = lanes 16g..16g+15 = half g >> 1, items 16 (g & 1) + c), A rows 0/1 = wm on user
+// a's k-groups of items 0-15 / 16-31, rows 2/3 the same for user b -- so one MFMA sums both
+// halves of a column (no cross-lane swap), and the accumulator is seeded with the tile's folded
+// per-pair term (GMF + bound - threshold, pair-interleaved in LDS so lanes 0-15 read their 4
+// seeds as one b128).  Lanes 0-15 end with the 64 test values; 4 ballots assemble the pair's
+// 64-bit pass mask with bit u*32 + item (the lane layout of the append).  Measured against the
+// earlier packed-dot epilogue (16 v_dot2c + a permlane32 swap per pair, 1.94 ms) and a
+// software-pipelined two-waves-per-SIMD variant (2.1-2.2 ms): 1.87 ms (tools/scan_ablation.hip,
+// profiles/r2_ncf_scan_variants.txt); splitting it (user a on the matrix pipe, user b by packed
+// dots) measured 2.03 vs 1.88 ms (round 3, profiles/r3c_ncf_epilogue_ab.txt): the VALU side is
+// the binding one.  DEBUG keeps a VALU epilogue (packed dots + swap).
+// DEEP (round 6, towers [2 h0, h1 <= 64, h2 <= 32, h3 <= 16]): layer 2 as above, then layer 3 on
+// the matrix pipe in place of the wm epilogue -- per user and item half g (items c / c + 16) two
+// v_mfma_f32_16x16x32_f16 whose A rows are W3's 16 units with the k-groups of the other item half
+// zeroed (the 16x16x32 B operand mixes items c and c + 16 across k-groups), accumulator seeded
+// with b3 -- relu by the clamp of the f32 -> f16 converts, and the prediction wp3 . relu(h3) as a
+// v_mfma_f32_16x16x16_f16 whose B operand is that accumulator as it lies (rows 4 (lane >> 4) + r =
+// units, columns = items) and whose A row idx = 2 user + g holds wp3: four of them chained on the
+// folded seeds leave the test values where the two-layer epilogue leaves them.  DEBUG uses the
+// same matrix epilogue (seeds = GMF only).  Two waves per SIMD (28 more live registers).
+// SHAPE 1 (HNM_OPT_SCAN_SHAPE, two-layer towers): layer 2 and the GMF on v_mfma_f32_16x16x32_f16,
+// everything outside the pair body as it is.  Per user 2 unit halves m x 2 item halves n x 2
+// k-steps s (8 x 16 cycles, the 4 x 32 of the other shape); the B operand clamp(P~ + Q~) of (n, s)
+// serves both m, and the lane's P~ fragment depends on (s, k-group) only, so a user takes 2
+// ds_read_b128 of P~ a tile instead of 4.  The four f32x4 accumulators of a user are seeded with
+// b2 (8 registers).  Epilogue: the converted accumulators m = 0, 1 of (user, n) are one B operand
+// of a 16x16x32 whose A row 2 user + n holds wm in that k order -- the same 4 chained MFMAs on
+// the folded seeds, the same output lanes, ballots and appends.  The GMF is 2 x 2 x 2 of the same
+// instruction (users as rows) stored into the same g7 table.  Its DEBUG pass takes this matrix
+// epilogue with GMF-only seeds and the deep DEBUG pass's dense store.  The tiles' rows are 128 B
+// with XOR-swizzled 16-B chunks (conflict-free for this shape's b128 reads: see so0 / so1).
+// 164 VGPRs, no scratch (SHAPE 0: 168 and one spilled register); three waves per SIMD.
+template <int MODE, bool DEEP = false, int SHAPE = 0>
+__global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kernel(ScanArgs A) {
+  constexpr bool S16 = SHAPE == 1;  // layer 2 and the GMF on v_mfma_f32_16x16x32_f16
+  static_assert(!(S16 && DEEP), "the deep scan has the 32x32x16 layout only");
+  // LDS row stride in halfs: 144 B (conflict-free b128 reads of the 32x32x16 operands: lane
+  // (j, h) reads row j) / S16: 128 B with the row's 16-B chunks XOR-swizzled (s16_chunk)
+  constexpr int RS = S16 ? 64 : 72;
+  constexpr int NU = 128;  // users per workgroup
+  // the matrix-pipe epilogue and its folded seed table (FOLD: GMF + bound - threshold; the deep
+  // and the S16 DEBUG pass: GMF alone)
+  constexpr bool FOLD = MODE == SCAN_THRESH || MODE == SCAN_SAMPLE ||
+                        ((DEEP || S16) && MODE == SCAN_DEBUG);
+  if (MODE == SCAN_SAMPLE && A.gate && *A.gate == 0) return;  // whole grid: gated off
+  __shared__ __attribute__((aligned(16))) _Float16 qs[2][TILE * RS];  // double-buffered tiles
+  __shared__ __attribute__((aligned(16))) _Float16 gs[2][TILE * RS];
+  __shared__ __attribute__((aligned(16))) _Float16 ps[NU * 64];
+  // per wave: the GMF table of its 32 users x the tile's 32 items (FOLD: folded test terms,
+  // pair-interleaved: g7 index below; DEBUG: gsm[row][item])
+  __shared__ __attribute__((aligned(16))) float gsm[4][32][33];
+  __shared__ float2 ut[4][32];  // FOLD: (tau or 0, cu) per user
+
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, j = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform: scalar loop state
+  // grid: x = item partition (NP a multiple of 8), y = user block -> the round-robin
+  // workgroup -> XCD placement keeps partition p on XCD p % 8 (its tiles stay in that L2)
+  const int upw = A.upw;  // <= 32 (NU / 4)
+  const int64_t ublk = (int64_t)blockIdx.y * 4 * upw;
+  const int64_t u0 = ublk + wave * upw;
+  const int nu = (int)std::max<int64_t>(0, std::min<int64_t>(upw, A.B - u0));
+  const int p = blockIdx.x;
+  const int64_t part_start = (int64_t)p * A.ipp;
+  const int64_t part_end = std::min<int64_t>(A.I, part_start + A.ipp);
+
+  for (int e = tid; e < NU * 8; e += 256) {
+    const int r = e >> 3, c = e & 7;
+    h8 v = {};
+    if (ublk + r < A.B) v = *reinterpret_cast<const h8*>(A.P16 + (ublk + r) * 64 + 8 * c);
+    *reinterpret_cast<h8*>(&ps[r * 64 + 8 * c]) = v;
+  }
+  // S16 (16x16x32: lane holds A[row lane & 15][k = 8 (lane >> 4) + e], B[k][col lane & 15] and
+  // D[row 4 (lane >> 4) + r][col lane & 15]): aw[2 m + s] = W2~ rows 16 m + c16, k-step s;
+  // ag[2 m + s] = the users 16 m + c16 of the wave; b2q[m] = the seeds of units 16 m + 4 g4 + r
+  const int c16 = lane & 15, g4 = lane >> 4;
+  h8 aw[4];
+  h8 ag[4];  // GMF A operand: this wave's users' wp*g_u rows
+  f32x16 b2c = {};
+  f32x4 b2q[2];
+  if constexpr (S16) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int ur = 16 * m + c16;
+        h8 z = {};
+        aw[2 * m + s] = *reinterpret_cast<const h8*>(A.W2h + ur * 64 + 32 * s + 8 * g4);
+        ag[2 * m + s] =
+            ur < nu ? *reinterpret_cast<const h8*>(A.WG16 + (u0 + ur) * 64 + 32 * s + 8 * g4) : z;
+      }
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) b2q[m][r] = A.b2s[16 * m + 4 * g4 + r];
+  } else {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) aw[s] = *reinterpret_cast<const h8*>(A.W2h + j * 64 + 16 * s + 8 * h);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      h8 z = {};
+      ag[s] = j < nu ? *reinterpret_cast<const h8*>(A.WG16 + (u0 + j) * 64 + 16 * s + 8 * h) : z;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) b2c[r] = A.b2s[mfma32_row(r, h)];
+  }
+  // epilogue A operands (16x16x32: lane holds A[row lane & 15][k = 8 (lane >> 4) + e])
+  h8 ewa[2], ewb[2];
+  h2 wm2[8];  // DEBUG: wm of this lane's accumulator rows, in pairs
+  h8 e3[2][2];  // DEEP: layer-3 A operands [item half g][accumulator half f]
+  h4 ep[4];     // DEEP: prediction A operands, wp3 in row idx = 2 user + g
+  f32x4 b3c;    // DEEP: layer-3 accumulator seeds (rows 4 (lane >> 4) + r)
+  if constexpr (DEEP) {
+    const int m = lane & 15, kg = lane >> 4;
+#pragma unroll
+    for (int g = 0; g < 2; ++g)
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          e3[g][f][e] = (kg & 1) == g ? A.W3h[m * 32 + mfma32_row(8 * f + e, kg >> 1)] : (_Float16)0.f;
+#pragma unroll
+    for (int idx = 0; idx < 4; ++idx)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ep[idx][e] = m == idx ? A.wph[4 * kg + e] : (_Float16)0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) b3c[r] = A.b3s[4 * kg + r];
+  } else if constexpr (S16) {
+    // the B operand of (user, item half n) is the lane's converted accumulators m = 0, 1 as one
+    // h8: k = 8 g4 + e is unit 16 (e >> 2) + 4 g4 + (e & 3); A row 2 user + n holds wm in that
+    // order (ewa[n]: user a, ewb[n]: user b), every k-group of the item half's own
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const _Float16 wv = A.wmh[16 * (e >> 2) + 4 * g4 + (e & 3)];
+        ewa[n][e] = c16 == n ? wv : (_Float16)0.f;
+        ewb[n][e] = c16 == 2 + n ? wv : (_Float16)0.f;
+      }
+  } else {
+    const int erow = lane & 15, eg = lane >> 4;
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const _Float16 wv = A.wmh[mfma32_row(8 * f + e, eg >> 1)];
+        ewa[f][e] = erow == (eg & 1) ? wv : (_Float16)0.f;
+        ewb[f][e] = erow == 2 + (eg & 1) ? wv : (_Float16)0.f;
+      }
+#pragma unroll
+    for (int r = 0; r < 16; r += 2)
+      wm2[r >> 1] = (h2){A.wmh[mfma32_row(r, h)], A.wmh[mfma32_row(r + 1, h)]};
+  }
+  float* const g7 = &gsm[wave][0][0];
+  // uniform scalars in SGPRs (the compiler cannot prove prm read-only, so it would keep them
+  // in VGPRs -- which are the scarce resource at three waves per SIMD)
+  const float cg = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(A.prm->cg)));
+  // per-user registers: lane u < nu follows user u0 + u
+  const float cu = lane < nu ? A.Cu[u0 + lane] : 0.f;
+  float tv = __builtin_inff(), eu = 0.f;
+  if (MODE == SCAN_THRESH && lane < nu) tv = A.tau[u0 + lane];
+  if (MODE == SCAN_DEBUG && lane < nu) eu = A.Eu[u0 + lane];
+  if (FOLD && lane < 32)
+    ut[wave][lane] = make_float2(MODE == SCAN_THRESH ? tv : 0.f, cu);  // lanes >= nu: (inf | 0, 0)
+  int ccount = 0;  // THRESH: appended items of user u0 + lane in this partition
+  int nm = INT_BIG, mpos = 0, mend = 0;
+  const bool masked = MODE == SCAN_THRESH && A.mptr != nullptr;
+  if (masked && lane < nu) {
+    const int64_t lo = A.mptr[u0 + lane], hi = A.mptr[u0 + lane + 1];
+    mpos = (int)mask_lower_bound(A.midx, lo, hi, (int)part_start);
+    mend = (int)hi;
+    nm = mpos < mend ? A.midx[mpos] : INT_BIG;
+  }
+  int32_t* seg = MODE == SCAN_THRESH ? A.buf + ((u0 * A.NP) + p) * (int64_t)A.capp : nullptr;
+  // the wave's 32 rows of candidate ids / test values (THRESH): buffer resources over the rows'
+  // segments, partition p's slots at row * segstride + slot (NP * capp * 128 < 2^31: cert_shape)
+  const __amdgpu_buffer_rsrc_t segrs = __builtin_amdgcn_make_buffer_rsrc(
+      MODE == SCAN_THRESH ? (void*)seg : (void*)A.buf, 0,
+      MODE == SCAN_THRESH ? (int)(32 * (int64_t)A.NP * A.capp * 4) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t segdrs = __builtin_amdgcn_make_buffer_rsrc(
+      MODE == SCAN_THRESH ? (void*)(A.segd + ((u0 * A.NP) + p) * (int64_t)A.capp) : (void*)A.buf,
+      0, MODE == SCAN_THRESH ? (int)(32 * (int64_t)A.NP * A.capp * 4) : 0, 0x00020000);
+  const int64_t segstride = (int64_t)A.NP * A.capp;  // next user's segment
+
+  const int64_t ntiles = part_end > part_start ? hnm_cdiv(part_end - part_start, TILE) : 0;
+  // tile staging: thread (row, c) moves 16 B of Q~ and of G~; tile t + 1 is fetched into
+  // registers while tile t is scored, then stored to the other LDS buffer (one barrier
+  // per tile)
+  // (row, 16-B chunk) of the thread's staging slot, recomputed where used: held across the
+  // tile loop they were spilled, and a spill reload's vmcnt wait also waits for the prefetch
+  auto srow_of = [&]() {
+    int v;
+    asm volatile("v_lshrrev_b32 %0, 3, %1" : "=v"(v) : "v"(tid));
+    return v;
+  };
+  auto sc_of = [&]() {
+    int v;
+    asm volatile("v_and_b32 %0, 7, %1" : "=v"(v) : "v"(tid));
+    return v;
+  };
+  h8 nq = {}, ng = {};
+  float nb = 0.f, nd = 0.f;  // per-item bound terms of lane j's next item
+  // the champion gather map is a SAMPLE-pass input only (compile-time null elsewhere: no
+  // dependent index loads, hence no mid-tile vmcnt waits, in the THRESH scan)
+  const int32_t* const sidx = MODE == SCAN_SAMPLE ? A.sidx : nullptr;
+  // 32-bit element offsets from the (uniform) table bases: the loads take an SGPR base and a
+  // VGPR offset, so no 64-bit per-lane addresses stay live across the tile loop (I * 64 <
+  // 2^31: ncf_cert_eligible)
+  auto fetch = [&](int64_t base) {
+    const int srow = srow_of(), sc = sc_of();
+    const int n = (int)(base + srow);
+    nq = (h8){};
+    ng = (h8){};
+    if (n < part_end) {
+      const int it = sidx ? sidx[n] : n;
+      nq = *reinterpret_cast<const h8*>(A.Q16 + (uint32_t)(it * 64 + 8 * sc));
+      ng = *reinterpret_cast<const h8*>(A.G16 + (uint32_t)(it * 64 + 8 * sc));
+    }
+    const int cj = (int)std::min<int64_t>(base + j, part_end - 1);
+    const int nj = sidx ? sidx[cj] : cj;
+    nb = A.Bi[(uint32_t)nj];
+    nd = A.Di[(uint32_t)nj];
+  };
+  auto stash = [&](int buf) {
+    const int srow = srow_of(), sc = sc_of();
+    // S16: chunk sc of row r lies at chunk position sc ^ (r >> 1 & 7) (the read side: s16 below)
+    const int pc = S16 ? sc ^ ((srow >> 1) & 7) : sc;
+    *reinterpret_cast<h8*>(&qs[buf][srow * RS + 8 * pc]) = nq;
+    *reinterpret_cast<h8*>(&gs[buf][srow * RS + 8 * pc]) = ng;
+  };
+  int64_t t = 0;
+  if (t < ntiles) {
+    fetch(part_start + t * TILE);
+    stash(0);
+  }
+  __syncthreads();
+  // drain every prologue load on every path into the loop (incl. ntiles == 0): otherwise the
+  // waitcnt pass merges a pending prologue load into the loop and waits vmcnt(0) -- i.e. for
+  // the tile prefetch too -- at the first use of a prologue register in every iteration
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) (gfx9 encoding: expcnt 7, lgkmcnt 15)
+  for (int cur = 0; t < ntiles; cur ^= 1) {
+    const int64_t base = part_start + t * TILE;
+    const int64_t tn = t + 1;
+    const float bj = nb, dj = nd;  // bound terms of this tile's item j (test units)
+    // the prefetch is the only global load in the tile body (vmcnt waits are in order: any
+    // later load's wait would also wait for it)
+    if (tn < ntiles) fetch(part_start + tn * TILE);
+    int lrow;  // lane (j, h)'s operand row offset in the tile buffers (recomputed: see srow_of)
+    asm volatile("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(lrow) : "v"(j), "v"(RS), "v"(8 * h));
+
+    // S16: lane (c16, g4)'s operand offsets in the tile buffers at k-steps 0 and 1, item half 0
+    // (half n: + 16 n RS).  Row r keeps chunk x at position x ^ (r >> 1 & 7): a b128 read's
+    // 16-lane groups pair eight lanes of one k-group with eight of the next, whose chunks differ
+    // in bit 0, and the rows' swizzles (0, 1, 6, 7 against 2, 3, 4, 5 on either row parity) keep
+    // the sixteen 16-B slots of the 256-B bank row distinct.  Recomputed per tile as lrow is.
+    int so0 = 0, so1 = 0;
+    if constexpr (S16) {
+      int ln;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+      const int x0 = (ln >> 4) ^ ((ln >> 1) & 7);
+      so0 = (ln & 15) * RS + 8 * x0;
+      so1 = (ln & 15) * RS + 8 * (x0 ^ 4);
+    }
+
+    if (nu > 0) {
+    if constexpr (S16) {  // GMF as 2 x 2 x 2 16x16x32: users 16 m + c16 x items c16 + 16 n
+      f32x4 ga[2][2] = {};
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          const h8 gb = *reinterpret_cast<const h8*>(&gs[cur][(s ? so1 : so0) + 16 * n * RS]);
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+            ga[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ag[2 * m + s], gb, ga[m][n], 0, 0, 0);
+        }
+      // the same folded table as below: lane (c16, g4) holds users 16 m + 4 g4 + r of items
+      // c16 + 16 n, whose bound terms lanes c16 + 16 n carry
+      constexpr float sgn = MODE == SCAN_THRESH ? 1.f : -1.f;
+      float bjn[2] = {0.f, 0.f}, djn[2] = {0.f, 0.f};
+      if (MODE != SCAN_DEBUG) {
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          bjn[n] = __shfl(bj, c16 + 16 * n);
+          djn[n] = __shfl(dj, c16 + 16 * n);
+        }
+      }
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * m + 4 * g4 + r;
+          const float2 tc = ut[wave][row];
+#pragma unroll
+          for (int n = 0; n < 2; ++n)
+            g7[(((row >> 1) * 16 + c16) << 2) + ((row & 1) << 1) + n] =
+                MODE == SCAN_DEBUG ? ga[m][n][r] * cg
+                                   : (ga[m][n][r] * cg + sgn * fmaf(tc.y, djn[n], bjn[n])) - tc.x;
+        }
+    } else {  // GMF of the wave's 32 users x 32 items, in score units
+      f32x16 gacc = {};
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        gacc = mfma16(ag[s], *reinterpret_cast<const h8*>(&gs[cur][lrow + 16 * s]), gacc);
+      if constexpr (FOLD) {
+        // folded test term gmf + sgn * e_i - tau (sgn = +1 for the threshold test, -1 for the
+        // sample's lower bound; the deep DEBUG pass: gmf alone)
+        constexpr float sgn = MODE == SCAN_THRESH ? 1.f : -1.f;
+        // (measured, round 5: the same stores from one lane base + immediate offsets -- 6 fewer
+        // VGPRs -- scheduled the pair loop's LDS reads differently, +1-2 % scan time)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = mfma32_row(r, h);
+          const float2 tc = ut[wave][row];
+          g7[(((row >> 1) * 16 + (j & 15)) << 2) + ((row & 1) << 1) + (j >> 4)] =
+              MODE == SCAN_DEBUG ? gacc[r] * cg : (gacc[r] * cg + sgn * fmaf(tc.y, dj, bj)) - tc.x;
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) gsm[wave][mfma32_row(r, h)][j] = gacc[r] * cg;
+      }
+    }
+    h8 q[4];  // S16: q[2 n + s] = Q~[item c16 + 16 n][k = 32 s + 8 g4 + e]
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      q[s] = *reinterpret_cast<const h8*>(
+          S16 ? &qs[cur][((s & 1) ? so1 : so0) + 16 * (s >> 1) * RS] : &qs[cur][lrow + 16 * s]);
+    const int64_t n = base + j;
+    const int64_t tile_end = std::min<int64_t>(base + TILE, part_end);
+    const int nv = (int)(tile_end - base);  // valid items of the tile
+    const uint64_t vm32 = nv >= 32 ? 0xffffffffull : ((1ull << nv) - 1ull);
+    unsigned mbits = 0;
+    if (masked) {  // scanned items are real items here (identity map in the THRESH pass)
+      uint64_t pend = __ballot(lane < 32 && nm < tile_end) & 0xffffffffull;
+      while (pend) {
+        const int u = __builtin_ctzll(pend);
+        pend &= pend - 1;
+        while (true) {
+          const int tgt = hnm_readlane_i(nm, u);
+          if (tgt >= tile_end) break;
+          if (lane == u) {
+            mbits |= 1u << (tgt - (int)base);
+            ++mpos;
+            nm = mpos < mend ? A.midx[mpos] : INT_BIG;
+          }
+        }
+      }
+    }
+
+    // user r, k-step s: pw[r * 64 + 16 s] (S16: pw[r * 64 + 32 s], the lane's k-group g4 -- one
+    // fragment serves both item halves)
+    const _Float16* pw = &ps[(wave * upw) * 64 + 8 * (S16 ? g4 : h)];
+    for (int u = 0; u < nu; u += 2) {
+      // user b = u + 1 even past nu (zero P~ rows; FOLD: folded term -inf / not stored)
+      const int ua = u, ub = u + 1;
+      const bool hasb = ub < nu;
+      const int uh = h ? ub : ua;
+      f32x16 acc0 = b2c, acc1 = b2c;
+      f32x4 ca[2][2], cb[2][2];  // S16: [unit half m][item half n], users a and b
+      if constexpr (S16) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int n = 0; n < 2; ++n) ca[m][n] = cb[m][n] = b2q[m];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const h8 pa = *reinterpret_cast<const h8*>(&pw[ua * 64 + 32 * s]);
+          const h8 pb = *reinterpret_cast<const h8*>(&pw[ub * 64 + 32 * s]);
+#pragma unroll
+          for (int n = 0; n < 2; ++n) {
+            h8 x = pa + q[2 * n + s];
+            x = __builtin_elementwise_min(__builtin_elementwise_max(x, (h8){}), (h8)(_Float16)1.f);
+            h8 y = pb + q[2 * n + s];
+            y = __builtin_elementwise_min(__builtin_elementwise_max(y, (h8){}), (h8)(_Float16)1.f);
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+              ca[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aw[2 * m + s], x, ca[m][n], 0, 0, 0);
+              cb[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aw[2 * m + s], y, cb[m][n], 0, 0, 0);
+            }
+          }
+        }
+      } else {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        // each fragment is read right before its MFMA (fewer live registers than a prefetch)
+        const h8 pa = *reinterpret_cast<const h8*>(&pw[ua * 64 + 16 * s]);
+        const h8 pb = *reinterpret_cast<const h8*>(&pw[ub * 64 + 16 * s]);
+        h8 x = pa + q[s];
+        x = __builtin_elementwise_min(__builtin_elementwise_max(x, (h8){}), (h8)(_Float16)1.f);
+        h8 y = pb + q[s];
+        y = __builtin_elementwise_min(__builtin_elementwise_max(y, (h8){}), (h8)(_Float16)1.f);
+        acc0 = mfma16(aw[s], x, acc0);
+        acc1 = mfma16(aw[s], y, acc1);
+      }
+      }  // !S16
+      if constexpr (FOLD) {
+        h8 ya[2], yb[2];  // S16: [item half n], the accumulators m = 0, 1 of the half as one h8
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          if constexpr (S16) {
+            ya[0][e] = (_Float16)ca[e >> 2][0][e & 3];
+            ya[1][e] = (_Float16)ca[e >> 2][1][e & 3];
+            yb[0][e] = (_Float16)cb[e >> 2][0][e & 3];
+            yb[1][e] = (_Float16)cb[e >> 2][1][e & 3];
+          } else {
+            ya[0][e] = (_Float16)acc0[e];
+            ya[1][e] = (_Float16)acc0[8 + e];
+            yb[0][e] = (_Float16)acc1[e];
+            yb[1][e] = (_Float16)acc1[8 + e];
+          }
+        }
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          ya[f] = __builtin_elementwise_min(__builtin_elementwise_max(ya[f], (h8){}), (h8)(_Float16)1.f);
+          yb[f] = __builtin_elementwise_min(__builtin_elementwise_max(yb[f], (h8){}), (h8)(_Float16)1.f);
+        }
+        // lanes 0-15: (a, c), (a, c + 16), (b, c), (b, c + 16); other lanes' rows are unused
+        f32x4 d = *reinterpret_cast<const f32x4*>(&g7[((u >> 1) * 16 + (lane & 15)) << 2]);
+        if constexpr (DEEP) {
+#pragma unroll
+          for (int uu = 0; uu < 2; ++uu)
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+              f32x4 t3 = b3c;
+              t3 = __builtin_amdgcn_mfma_f32_16x16x32_f16(e3[g][0], uu ? yb[0] : ya[0], t3, 0, 0, 0);
+              t3 = __builtin_amdgcn_mfma_f32_16x16x32_f16(e3[g][1], uu ? yb[1] : ya[1], t3, 0, 0, 0);
+              h4 z = {(_Float16)t3[0], (_Float16)t3[1], (_Float16)t3[2], (_Float16)t3[3]};
+              z = __builtin_elementwise_min(__builtin_elementwise_max(z, (h4){}), (h4)(_Float16)1.f);
+              d = __builtin_amdgcn_mfma_f32_16x16x16f16(ep[2 * uu + g], z, d, 0, 0, 0);
+            }
+        } else {
+          d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewa[0], ya[0], d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewa[1], ya[1], d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewb[0], yb[0], d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewb[1], yb[1], d, 0, 0, 0);
+        }
+        const uint64_t vmask = vm32 | (hasb ? vm32 << 32 : 0ull);
+        if (MODE == SCAN_DEBUG) {  // DEEP: approx and the whole bound, per pair, scaled units
+          float bjr[2], djr[2];  // the bound terms of items c and c + 16 (lanes c, c + 16)
+#pragma unroll
+          for (int q2 = 0; q2 < 2; ++q2) {
+            bjr[q2] = __shfl(bj, (lane & 15) + 16 * q2);
+            djr[q2] = __shfl(dj, (lane & 15) + 16 * q2);
+          }
+          const float cua = hnm_readlane_f(cu, ua), cub = hnm_readlane_f(cu, ub);
+          const float eua = hnm_readlane_f(eu, ua), eub = hnm_readlane_f(eu, ub);
+          if (lane < 16) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int it = lane + 16 * (r & 1);
+              if ((vmask >> (32 * (r >> 1) + it)) & 1) {
+                const int64_t o = (u0 + ua + (r >> 1)) * A.ldo + base + it;
+                A.dense[o] = d[r];
+                A.dense2[o] = (r >> 1 ? eub : eua) + fmaf(r >> 1 ? cub : cua, djr[r & 1], bjr[r & 1]);
+              }
+            }
+          }
+        } else if (MODE == SCAN_SAMPLE) {
+          if (lane < 16) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int it = lane + 16 * (r & 1);
+              if ((vmask >> (32 * (r >> 1) + it)) & 1)
+                A.dense[(u0 + ua + (r >> 1)) * A.ldo + base + it] = d[r];  // score - e_i
+            }
+          }
+        } else {
+          const uint64_t m0 = __ballot(!(d[0] < 0.f)) & 0xffffull;
+          const uint64_t m1 = __ballot(!(d[1] < 0.f)) & 0xffffull;
+          const uint64_t m2 = __ballot(!(d[2] < 0.f)) & 0xffffull;
+          const uint64_t m3 = __ballot(!(d[3] < 0.f)) & 0xffffull;
+          uint64_t m = (m0 | (m1 << 16) | (m2 << 32) | (m3 << 48)) & vmask;  // !(score + e_i < tau)
+          // filtered items of the two users, looked up only for a pair with a pass (a few % of
+          // pairs): two readlanes per pair in the issue-bound loop cost ~7 % of the scan
+          if (masked && m) {  // uniform
+            const unsigned mba = (unsigned)hnm_readlane_i((int)mbits, ua);
+            const unsigned mbb = (unsigned)hnm_readlane_i((int)mbits, ub);
+            m &= ~((uint64_t)mba | ((uint64_t)mbb << 32));
+          }
+          if (m) {
+            // lane c < 16 holds d[0..3] = the test values of (a, c), (a, c + 16), (b, c),
+            // (b, c + 16): it appends its passing pairs itself -- the id and, for the
+            // re-scoring's best-first order, the test value -- at the slot the pair's rank in the
+            // pass mask gives (no cross-lane moves; the store addresses are uniform bases)
+            const int ca = hnm_readlane_i(ccount, ua), cb = hnm_readlane_i(ccount, ub);
+            if (lane < 16) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int uu = r >> 1, it = lane + 16 * (r & 1);
+                const unsigned mu = (unsigned)(m >> (32 * uu));
+                const int ps = (uu ? cb : ca) + __builtin_popcount(mu & ((1u << it) - 1u));
+                if (((mu >> it) & 1u) && ps < A.capp) {
+                  // buffer stores: uniform row offset in an SGPR, the slot in one VGPR (the
+                  // tile loop runs at the 168-VGPR limit; 64-bit addresses here spilled)
+                  const int so = (uu ? ub : ua) * (int)segstride * 4;
+                  __builtin_amdgcn_raw_buffer_store_b32((int)(base + it), segrs, ps * 4, so, 0);
+                  __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(d[r]), segdrs, ps * 4, so, 0);
+                }
+              }
+            }
+            if (lane == ua) ccount += __builtin_popcount((unsigned)m);
+            if (lane == ub && hasb) ccount += __builtin_popcount((unsigned)(m >> 32));
+          }
+        }
+      } else {  // DEBUG: approx score and the whole bound, per pair, in scaled units
+        float ma = 0.f, mb = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          h2 ya = {(_Float16)acc0[r], (_Float16)acc0[r + 1]};
+          ya = __builtin_elementwise_min(__builtin_elementwise_max(ya, (h2){}), (h2)(_Float16)1.f);
+          h2 yb = {(_Float16)acc1[r], (_Float16)acc1[r + 1]};
+          yb = __builtin_elementwise_min(__builtin_elementwise_max(yb, (h2){}), (h2)(_Float16)1.f);
+          ma = __builtin_amdgcn_fdot2(ya, wm2[r >> 1], ma, false);
+          mb = __builtin_amdgcn_fdot2(yb, wm2[r >> 1], mb, false);
+        }
+        // after the swap lanes 0-31 hold user a's total, lanes 32-63 user b's
+        const auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(ma), __float_as_uint(mb),
+                                                          false, false);
+        const float score = (__uint_as_float(sw2[0]) + __uint_as_float(sw2[1])) + gsm[wave][uh][j];
+        const float cuh = h ? hnm_readlane_f(cu, ub) : hnm_readlane_f(cu, ua);
+        const float euh = h ? hnm_readlane_f(eu, ub) : hnm_readlane_f(eu, ua);
+        if (n < part_end && (h == 0 || hasb)) {
+          A.dense[(u0 + uh) * A.ldo + n] = score;
+          A.dense2[(u0 + uh) * A.ldo + n] = euh + fmaf(cuh, dj, bj);
+        }
+      }
+    }
+    }  // nu > 0
+    if (tn < ntiles) stash(cur ^ 1);
+    __syncthreads();
+    t = tn;
+  }
+  if (MODE == SCAN_THRESH && lane < nu) A.cnt[(u0 + lane) * A.NP + p] = ccount;
+}
+
+template <int MODE>
+void launch_scan(hnm_ctx* ctx, dim3 grid, const ScanArgs& a) {
+  // HNM_OPT_SCAN_SHAPE picks the two-layer scan's layout, every pass of a call alike (the deep
+  // scan has the 32x32x16 layout only)
+  if (a.W3h)
+    hipLaunchKernelGGL((ncf16_scan_kernel<MODE, true>), grid, dim3(256), 0, ctx->stream, a);
+  else if (ctx->scan_shape)
+    hipLaunchKernelGGL((ncf16_scan_kernel<MODE, false, 1>), grid, dim3(256), 0, ctx->stream, a);
+  else
+    hipLaunchKernelGGL((ncf16_scan_kernel<MODE, false, 0>), grid, dim3(256), 0, ctx->stream, a);
+}
+
+}  // namespace
+
+void cert_launch_scan(hnm_ctx* ctx, int mode, dim3 grid, const ScanArgs& a) {
+  if (mode == SCAN_SAMPLE) launch_scan<SCAN_SAMPLE>(ctx, grid, a);
+  else if (mode == SCAN_THRESH) launch_scan<SCAN_THRESH>(ctx, grid, a);
+  else launch_scan<SCAN_DEBUG>(ctx, grid, a);
+}

@@ -1,4 +1,5 @@
-// Shared between ncf.hip (exact fp32 kernels) and ncf_cert.hip (certified f16 pre-filter).
+// Shared between ncf.hip (exact fp32 kernels) and ncf_cert.hip with its units (certified f16
+// pre-filter; what those units share among themselves: ncf_cert_internal.h).
 #pragma once
 #include "hnm_internal.h"
 
@@ -13,7 +14,7 @@ struct NcfTabs {
 };
 
 // Column c of the row wp_gmf * g_u (gather_scale_kernel in ncf.hip, ncf_tables_kernel in
-// ncf_cert.hip): ok = the row's id is in range.
+// ncf_cert_params.hip): ok = the row's id is in range.
 __device__ __forceinline__ float ncf_gather_scale(const float* __restrict__ tab, int64_t id,
                                                   int ld, int d, const float* __restrict__ s,
                                                   int c, bool ok) {
@@ -58,10 +59,9 @@ hnm_status ncf_deep_cert_debug(hnm_ctx* ctx, const hnm_ncf_deep_weights* dw, con
 bool ncf_cert_eligible(const hnm_ncf_weights* w, int K);
 // strided: the call may run the gated strided sample (HNM_OPT_STRIDED), whose per-row scratch
 // ([B, I / 8] values) is carved only then; begin and finish of one call must agree on it
-size_t ncf_cert_bytes(int64_t B, int64_t I, int K, int num_cus, int wg, bool strided);
-int ncf_cert_wg(const hnm_ctx* ctx);  // scan workgroups per CU of the selected variant
-// The per-call tables and the bound statistics of their rows in one launch (ncf_tables_kernel,
-// HNM_OPT_NCF_TABLES), for a call that goes on to ncf_cert_begin / ncf_cert_debug with the same
+size_t ncf_cert_bytes(const hnm_ctx* ctx, int64_t B, int64_t I, int K, bool strided);
+// The per-call tables and the bound statistics of their rows in one launch (ncf_tables_kernel in
+// ncf_cert_params.hip, HNM_OPT_NCF_TABLES), for a call that goes on to ncf_cert_begin / ncf_cert_debug with the same
 // (K, scratch, strided): P_u, wp * g_u and -- unless w->item_proj is set -- Q_i are written to
 // Pu / WGu / Qi [*, 64], A_u, C_u, B_i, D_i and the maxima's partials into the scratch.  The
 // caller checks the shape: two-layer tower, h1 <= 64, mf <= 64 a multiple of 4, h0 a multiple of

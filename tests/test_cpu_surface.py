@@ -224,6 +224,16 @@ def test_build_tracks_every_csrc_header(tmp_path, monkeypatch):
     assert build._deps_mtime() == later
 
 
+def test_build_sources_list_every_csrc_unit():
+    """Every csrc/*.hip is in build.SOURCES and every entry exists: a unit left off the list still
+    links (-shared tolerates undefined symbols) and fails only when the library is loaded."""
+    import glob
+    from hnm_recommendation_amd import build
+    units = sorted(os.path.basename(p) for p in glob.glob(os.path.join(build.CSRC, "*.hip")))
+    assert len(build.SOURCES) == len(set(build.SOURCES))
+    assert sorted(build.SOURCES) == units
+
+
 def test_ncf_shard_scorer_dispatch():
     """sharding.ncf_shard_topk gives the fused two-phase scorer for the default tower and
     ncf_deep_shard_topk (single-phase, k <= 64) for any other tower (no GPU work at

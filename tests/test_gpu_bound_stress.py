@@ -217,7 +217,7 @@ def test_ncf_strided_sample_gate(kind):
 def test_ncf_best_first_rescoring(kind):
     """Rows whose scan bound came from a poor sample append hundreds of candidates; the
     re-scoring scores the 64 best (by the scan's test value) first and then only candidates
-    that pass against their exact K-th (ncf_cert.hip ncf_rescore_kernel, round 5).  Bitwise the
+    that pass against their exact K-th (ncf_cert_rescore.hip ncf_rescore_kernel, round 5).  Bitwise the
     exact scan's top-K, with far fewer exact re-scores than appended candidates (the bench's
     weight sets at the H&M shape: personal 306 appended / 64 re-scored a row, norms 598 / 64)."""
     U, B = syn.HM_USERS, 512

@@ -1,4 +1,4 @@
-"""GPU: the two layouts of the certified NeuralCF scan (ncf_cert.hip ncf16_scan_kernel,
+"""GPU: the two layouts of the certified NeuralCF scan (ncf_cert_scan.hip ncf16_scan_kernel,
 HNM_OPT_SCAN_SHAPE): layer 2 and the GMF on v_mfma_f32_16x16x32_f16 (1) or on
 v_mfma_f32_32x32x16_f16 (0).
 

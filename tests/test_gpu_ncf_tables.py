@@ -1,4 +1,4 @@
-"""GPU: the one-launch NeuralCF tables (ncf_cert.hip ncf_tables_kernel, HNM_OPT_NCF_TABLES).
+"""GPU: the one-launch NeuralCF tables (ncf_cert_params.hip ncf_tables_kernel, HNM_OPT_NCF_TABLES).
 
 With the option at 1 the certified two-layer path builds P_u, wp * g_u, Q_i and the bound
 statistics of their rows (A_u, C_u, B_i, D_i, the six maxima) in one launch; at 0 it runs the

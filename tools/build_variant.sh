@@ -9,7 +9,9 @@ python -c "import sys; sys.path.insert(0, '$ROOT'); from hnm_recommendation_amd.
 mkdir -p "$ROOT/tools/bin/obj_$TAG"
 base=$(basename "$SRC" .hip)
 # the variant source must carry the name of the object it replaces (e.g. an old version in
-# another directory: git show HEAD:.../ncf_cert.hip > /tmp/old/ncf_cert.hip)
+# another directory: git show HEAD:.../ncf_cert_scan.hip > /tmp/old/ncf_cert_scan.hip).  A -D flag
+# reaches that unit alone: RESCORE_PERSIST / RESCORE_BEST_FIRST_AB are ncf_cert_rescore.hip's,
+# CERT_CHAMPIONS_AB is ncf_cert.hip's (cert_shape).
 [ -f "$ROOT/build/obj/$base.o" ] || { echo "no build/obj/$base.o to replace"; exit 1; }
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I"$ROOT/hnm_recommendation_amd/csrc" -I"$ROOT/include" "$@" -c "$SRC" -o "$ROOT/tools/bin/obj_$TAG/$base.o"
 objs=()

@@ -3,11 +3,12 @@
 // clock warm-up, so scan variants can be compared without the rest of the step.  Both layouts
 // of the two-layer scan are timed, alternating (SHAPE 0: 32x32x16, 1: 16x16x32;
 // HNM_OPT_SCAN_SHAPE).
-// Diagnostic build only:
+// Diagnostic build only (the scan unit is included as text: the kernel is private to it;
+// cert_shape comes from ncf_cert.o through ncf_cert_internal.h):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -c tools/scan_ablation.hip -o build/scan_ablation.o
-//   hipcc --offload-arch=gfx950 build/scan_ablation.o <every build/obj/*.o but ncf_cert.o> \
+//   hipcc --offload-arch=gfx950 build/scan_ablation.o <every build/obj/*.o but ncf_cert_scan.o> \
 //         -L/opt/rocm/lib -lrccl -o tools/bin/scan_ablation
-#include "../hnm_recommendation_amd/csrc/ncf_cert.hip"
+#include "../hnm_recommendation_amd/csrc/ncf_cert_scan.hip"
 
 #include <vector>
 
@@ -46,7 +47,7 @@ static float time_scan(dim3 grid, const ScanArgs& a) {
 
 int main() {
   const int64_t B = 4096, I = 105542;
-  const CertShape sh = cert_shape(B, I, 12, 256, CERT_WG_PER_CU);
+  const CertShape sh = cert_shape(B, I, 12, 256);
   ScanArgs a{};
   a.P16 = dev_fill<_Float16>(B * 64, -0.25f, 0.25f, 1);
   a.WG16 = dev_fill<_Float16>(B * 64, -0.5f, 0.5f, 2);
