@@ -49,7 +49,12 @@ __device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
 // instruction (users as rows) stored into the same g7 table.  Its DEBUG pass takes this matrix
 // epilogue with GMF-only seeds and the deep DEBUG pass's dense store.  The tiles' rows are 128 B
 // with XOR-swizzled 16-B chunks (conflict-free for this shape's b128 reads: see so0 / so1).
-// 164 VGPRs, no scratch (SHAPE 0: 168 and one spilled register); three waves per SIMD.
+// THRESH pass test (every layout): a pair's four compares are OR-ed first and the iteration ends
+// there when no lane of 0-15 passes (~96 % of them); the bit layout, the history lookup and the
+// ranks are built only behind that.  The test runs one pair late, among the next pair's layer-2
+// MFMAs (pass_test / dprev below).  Kernel only at the bench shape (tools/scan_ablation.hip,
+// profiles/ncf_scan_issue_ab.txt): 1.710 -> 1.632 ms for the early exit, -> 1.611 ms run late.
+// 168 VGPRs, no scratch (SHAPE 0: 168 and four spilled registers); three waves per SIMD.
 template <int MODE, bool DEEP = false, int SHAPE = 0>
 __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kernel(ScanArgs A) {
   constexpr bool S16 = SHAPE == 1;  // layer 2 and the GMF on v_mfma_f32_16x16x32_f16
@@ -80,8 +85,11 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
   const int64_t u0 = ublk + wave * upw;
   const int nu = (int)std::max<int64_t>(0, std::min<int64_t>(upw, A.B - u0));
   const int p = blockIdx.x;
-  const int64_t part_start = (int64_t)p * A.ipp;
-  const int64_t part_end = std::min<int64_t>(A.I, part_start + A.ipp);
+  // Item and tile indices are 32-bit: A.I * 64 < 2^31 (ncf_cert_eligible; a sample pass scans
+  // no more than the catalogue), ipp is I / NP rounded up to a tile and p * ipp < I (NP =
+  // cdiv(I, ipp)), so every index below, one tile past a partition's end included, is < 2^27.
+  const int part_start = p * (int)A.ipp;
+  const int part_end = std::min<int>((int)A.I, part_start + (int)A.ipp);
 
   for (int e = tid; e < NU * 8; e += 256) {
     const int r = e >> 3, c = e & 7;
@@ -201,7 +209,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
       0, MODE == SCAN_THRESH ? (int)(32 * (int64_t)A.NP * A.capp * 4) : 0, 0x00020000);
   const int64_t segstride = (int64_t)A.NP * A.capp;  // next user's segment
 
-  const int64_t ntiles = part_end > part_start ? hnm_cdiv(part_end - part_start, TILE) : 0;
+  const int ntiles = part_end > part_start ? (part_end - part_start + TILE - 1) / TILE : 0;
   // tile staging: thread (row, c) moves 16 B of Q~ and of G~; tile t + 1 is fetched into
   // registers while tile t is scored, then stored to the other LDS buffer (one barrier
   // per tile)
@@ -225,7 +233,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
   // 32-bit element offsets from the (uniform) table bases: the loads take an SGPR base and a
   // VGPR offset, so no 64-bit per-lane addresses stay live across the tile loop (I * 64 <
   // 2^31: ncf_cert_eligible)
-  auto fetch = [&](int64_t base) {
+  auto fetch = [&](int base) {
     const int srow = srow_of(), sc = sc_of();
     const int n = (int)(base + srow);
     nq = (h8){};
@@ -235,7 +243,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
       nq = *reinterpret_cast<const h8*>(A.Q16 + (uint32_t)(it * 64 + 8 * sc));
       ng = *reinterpret_cast<const h8*>(A.G16 + (uint32_t)(it * 64 + 8 * sc));
     }
-    const int cj = (int)std::min<int64_t>(base + j, part_end - 1);
+    const int cj = (int)std::min<int>(base + j, part_end - 1);
     const int nj = sidx ? sidx[cj] : cj;
     nb = A.Bi[(uint32_t)nj];
     nd = A.Di[(uint32_t)nj];
@@ -247,7 +255,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
     *reinterpret_cast<h8*>(&qs[buf][srow * RS + 8 * pc]) = nq;
     *reinterpret_cast<h8*>(&gs[buf][srow * RS + 8 * pc]) = ng;
   };
-  int64_t t = 0;
+  int t = 0;
   if (t < ntiles) {
     fetch(part_start + t * TILE);
     stash(0);
@@ -258,8 +266,8 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
   // the tile prefetch too -- at the first use of a prologue register in every iteration
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) (gfx9 encoding: expcnt 7, lgkmcnt 15)
   for (int cur = 0; t < ntiles; cur ^= 1) {
-    const int64_t base = part_start + t * TILE;
-    const int64_t tn = t + 1;
+    const int base = part_start + t * TILE;
+    const int tn = t + 1;
     const float bj = nb, dj = nd;  // bound terms of this tile's item j (test units)
     // the prefetch is the only global load in the tile body (vmcnt waits are in order: any
     // later load's wait would also wait for it)
@@ -344,8 +352,8 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
     for (int s = 0; s < 4; ++s)
       q[s] = *reinterpret_cast<const h8*>(
           S16 ? &qs[cur][((s & 1) ? so1 : so0) + 16 * (s >> 1) * RS] : &qs[cur][lrow + 16 * s]);
-    const int64_t n = base + j;
-    const int64_t tile_end = std::min<int64_t>(base + TILE, part_end);
+    const int n = base + j;
+    const int tile_end = std::min<int>(base + TILE, part_end);
     const int nv = (int)(tile_end - base);  // valid items of the tile
     const uint64_t vm32 = nv >= 32 ? 0xffffffffull : ((1ull << nv) - 1ull);
     unsigned mbits = 0;
@@ -369,6 +377,59 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
     // user r, k-step s: pw[r * 64 + 16 s] (S16: pw[r * 64 + 32 s], the lane's k-group g4 -- one
     // fragment serves both item halves)
     const _Float16* pw = &ps[(wave * upw) * 64 + 8 * (S16 ? g4 : h)];
+    // THRESH: the pass test and the appends of pair (u, u + 1), whose test values d lanes 0-15
+    // hold
+    auto pass_test = [&](const f32x4 d, const int u) {
+      const int ua = u, ub = u + 1;
+      const bool hasb = ub < nu;
+      // !(score + e_i < tau), ordered compares: a NaN or -0 test value passes
+      const uint64_t b0 = __ballot(!(d[0] < 0.f)), b1 = __ballot(!(d[1] < 0.f));
+      const uint64_t b2 = __ballot(!(d[2] < 0.f)), b3 = __ballot(!(d[3] < 0.f));
+      // ~96 % of pair iterations append nothing: those end at the OR of the four compares
+      // over lanes 0-15.  It may count a pair vmask excludes (a padded item of a partial last
+      // tile), which the exact mask below then drops.
+      if (((b0 | b1 | b2 | b3) & 0xffffull) == 0) return;  // uniform
+      const uint64_t m0 = b0 & 0xffffull, m1 = b1 & 0xffffull;
+      const uint64_t m2 = b2 & 0xffffull, m3 = b3 & 0xffffull;
+      const uint64_t vmask = vm32 | (hasb ? vm32 << 32 : 0ull);
+      uint64_t m = (m0 | (m1 << 16) | (m2 << 32) | (m3 << 48)) & vmask;
+      // filtered items of the two users, looked up only for a pair with a pass (a few % of
+      // pairs): two readlanes per pair in the issue-bound loop cost ~7 % of the scan
+      if (masked && m) {  // uniform
+        const unsigned mba = (unsigned)hnm_readlane_i((int)mbits, ua);
+        const unsigned mbb = (unsigned)hnm_readlane_i((int)mbits, ub);
+        m &= ~((uint64_t)mba | ((uint64_t)mbb << 32));
+      }
+      if (m) {
+        // lane c < 16 holds d[0..3] = the test values of (a, c), (a, c + 16), (b, c),
+        // (b, c + 16): it appends its passing pairs itself -- the id and, for the
+        // re-scoring's best-first order, the test value -- at the slot the pair's rank in the
+        // pass mask gives (no cross-lane moves; the store addresses are uniform bases)
+        const int ca = hnm_readlane_i(ccount, ua), cb = hnm_readlane_i(ccount, ub);
+        if (lane < 16) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int uu = r >> 1, it = lane + 16 * (r & 1);
+            const unsigned mu = (unsigned)(m >> (32 * uu));
+            const int ps = (uu ? cb : ca) + __builtin_popcount(mu & ((1u << it) - 1u));
+            if (((mu >> it) & 1u) && ps < A.capp) {
+              // buffer stores: uniform row offset in an SGPR, the slot in one VGPR (the
+              // tile loop runs at the 168-VGPR limit; 64-bit addresses here spilled)
+              const int so = (uu ? ub : ua) * (int)segstride * 4;
+              __builtin_amdgcn_raw_buffer_store_b32((int)(base + it), segrs, ps * 4, so, 0);
+              __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(d[r]), segdrs, ps * 4, so, 0);
+            }
+          }
+        }
+        if (lane == ua) ccount += __builtin_popcount((unsigned)m);
+        if (lane == ub && hasb) ccount += __builtin_popcount((unsigned)(m >> 32));
+      }
+    };
+    // The test of a pair runs one iteration late, among the next pair's layer-2 MFMAs (and after
+    // the loop for the last pair): placed behind the pair's own epilogue it waited for the last
+    // MFMA of the chain and then held the wave's next LDS reads back by its compares and scalar
+    // tail.  The seed of the first iteration passes nothing.
+    f32x4 dprev = {-1.f, -1.f, -1.f, -1.f};
     for (int u = 0; u < nu; u += 2) {
       // user b = u + 1 even past nu (zero P~ rows; FOLD: folded term -inf / not stored)
       const int ua = u, ub = u + 1;
@@ -412,6 +473,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         acc1 = mfma16(aw[s], y, acc1);
       }
       }  // !S16
+      if constexpr (MODE == SCAN_THRESH) pass_test(dprev, u - 2);  // the pair before this one
       if constexpr (FOLD) {
         h8 ya[2], yb[2];  // S16: [item half n], the accumulators m = 0, 1 of the half as one h8
 #pragma unroll
@@ -453,7 +515,6 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
           d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewb[0], yb[0], d, 0, 0, 0);
           d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewb[1], yb[1], d, 0, 0, 0);
         }
-        const uint64_t vmask = vm32 | (hasb ? vm32 << 32 : 0ull);
         if (MODE == SCAN_DEBUG) {  // DEEP: approx and the whole bound, per pair, scaled units
           float bjr[2], djr[2];  // the bound terms of items c and c + 16 (lanes c, c + 16)
 #pragma unroll
@@ -463,6 +524,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
           }
           const float cua = hnm_readlane_f(cu, ua), cub = hnm_readlane_f(cu, ub);
           const float eua = hnm_readlane_f(eu, ua), eub = hnm_readlane_f(eu, ub);
+          const uint64_t vmask = vm32 | (hasb ? vm32 << 32 : 0ull);
           if (lane < 16) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -475,6 +537,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
             }
           }
         } else if (MODE == SCAN_SAMPLE) {
+          const uint64_t vmask = vm32 | (hasb ? vm32 << 32 : 0ull);
           if (lane < 16) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -484,42 +547,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
             }
           }
         } else {
-          const uint64_t m0 = __ballot(!(d[0] < 0.f)) & 0xffffull;
-          const uint64_t m1 = __ballot(!(d[1] < 0.f)) & 0xffffull;
-          const uint64_t m2 = __ballot(!(d[2] < 0.f)) & 0xffffull;
-          const uint64_t m3 = __ballot(!(d[3] < 0.f)) & 0xffffull;
-          uint64_t m = (m0 | (m1 << 16) | (m2 << 32) | (m3 << 48)) & vmask;  // !(score + e_i < tau)
-          // filtered items of the two users, looked up only for a pair with a pass (a few % of
-          // pairs): two readlanes per pair in the issue-bound loop cost ~7 % of the scan
-          if (masked && m) {  // uniform
-            const unsigned mba = (unsigned)hnm_readlane_i((int)mbits, ua);
-            const unsigned mbb = (unsigned)hnm_readlane_i((int)mbits, ub);
-            m &= ~((uint64_t)mba | ((uint64_t)mbb << 32));
-          }
-          if (m) {
-            // lane c < 16 holds d[0..3] = the test values of (a, c), (a, c + 16), (b, c),
-            // (b, c + 16): it appends its passing pairs itself -- the id and, for the
-            // re-scoring's best-first order, the test value -- at the slot the pair's rank in the
-            // pass mask gives (no cross-lane moves; the store addresses are uniform bases)
-            const int ca = hnm_readlane_i(ccount, ua), cb = hnm_readlane_i(ccount, ub);
-            if (lane < 16) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const int uu = r >> 1, it = lane + 16 * (r & 1);
-                const unsigned mu = (unsigned)(m >> (32 * uu));
-                const int ps = (uu ? cb : ca) + __builtin_popcount(mu & ((1u << it) - 1u));
-                if (((mu >> it) & 1u) && ps < A.capp) {
-                  // buffer stores: uniform row offset in an SGPR, the slot in one VGPR (the
-                  // tile loop runs at the 168-VGPR limit; 64-bit addresses here spilled)
-                  const int so = (uu ? ub : ua) * (int)segstride * 4;
-                  __builtin_amdgcn_raw_buffer_store_b32((int)(base + it), segrs, ps * 4, so, 0);
-                  __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(d[r]), segdrs, ps * 4, so, 0);
-                }
-              }
-            }
-            if (lane == ua) ccount += __builtin_popcount((unsigned)m);
-            if (lane == ub && hasb) ccount += __builtin_popcount((unsigned)(m >> 32));
-          }
+          dprev = d;  // THRESH: tested in the next iteration
         }
       } else {  // DEBUG: approx score and the whole bound, per pair, in scaled units
         float ma = 0.f, mb = 0.f;
@@ -544,6 +572,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         }
       }
     }
+    if constexpr (MODE == SCAN_THRESH) pass_test(dprev, (nu - 1) & ~1);  // the tile's last pair
     }  // nu > 0
     if (tn < ntiles) stash(cur ^ 1);
     __syncthreads();
