@@ -156,6 +156,11 @@ _SIGS = {
     "hnm_mask_gather_csr": (_i32, [_p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p]),
     "hnm_rank_metrics_f64": (_i32, [_p, _p, _i64, _i64, _p, C.c_int, _p, _p, _i64, _p, _p, _p,
                                     _p, _p]),
+    # ctx, item_ids, n, days_ago, day_weight, num_items, num_days, slab, count, pop
+    "hnm_popularity_fit_f64": (_i32, [_p, _p, _i64, _p, _p, _i64, _i64, _i64, _p, _p]),
+    # ctx, order, order_val, R, rank, num_items, mask_ptr, mask_idx, B, k, chunk, out_val, out_idx
+    "hnm_popularity_topk_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, _p, _p, _i64, C.c_int, C.c_int,
+                                       _p, _p]),
 }
 
 _lib = None

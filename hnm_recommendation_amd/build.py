@@ -17,7 +17,8 @@ BUILD = os.path.join(REPO, "build", "obj")
 LIB = os.path.join(PKG, "libhnm_mi355x.so")
 SOURCES = ["api.hip", "score.hip", "dot_cert.hip", "ncf.hip", "ncf_cert.hip", "ncf_cert_params.hip",
            "ncf_cert_scan.hip", "ncf_cert_rescore.hip", "ncf_deep.hip", "graph.hip", "widedeep.hip",
-           "widedeep_cert.hip", "widedeep_rescore.hip", "widedeep_features.hip", "eval.hip", "topk_sort.hip", "collective.hip"]
+           "widedeep_cert.hip", "widedeep_rescore.hip", "widedeep_features.hip", "eval.hip", "topk_sort.hip", "collective.hip",
+           "popularity.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]

@@ -2,7 +2,9 @@
 from .lightgcn import LightGCN
 from .matrix_factorization import MatrixFactorization
 from .neural_cf import NeuralCF
+from .popularity import PopularityBaseline
 from .base import UserHistory
 from .wide_deep import WideDeep
 
-__all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "UserHistory"]
+__all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
+           "UserHistory"]

@@ -18,6 +18,9 @@ article-metadata tables (out of scope: SURVEY §2):
   ONE fused call (`recommend_with_scores`: scoring + in-kernel history mask + top-k on the
   GPU); per-user errors (unknown user) become `{"user_id", "error"}` entries as in the
   reference loop (`:396-411`).
+* `Recommender.add_popularity_baseline` -- `_load_popularity_baseline` (`serve.py:260-280`):
+  the fitted `PopularityBaseline` under "popularity_baseline", the model `"best"` falls back
+  to when no checkpoint carries a `test_map` (`:415-430`).
 """
 from __future__ import annotations
 
@@ -29,13 +32,15 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import torch
 
-from .models import LightGCN, MatrixFactorization, NeuralCF, WideDeep
+from .models import LightGCN, MatrixFactorization, NeuralCF, PopularityBaseline, WideDeep
 from .models.base import UserHistory
 
 logger = logging.getLogger(__name__)
 
 # serve.py:56: RecommendationRequest.num_items = Field(12, ge=1, le=100)
 MAX_NUM_ITEMS = 100
+
+BASELINE = "popularity_baseline"  # serve.py:273: the name the reference registers it under
 
 # serve.py:238-248, tested in this order
 _DISPATCH = (("matrix_factorization", MatrixFactorization), ("neural_cf", NeuralCF),
@@ -82,13 +87,20 @@ class Recommender:
     'metrics' entry holds, `serve.py:203`); user_history: {user_idx: set(item_idx)} (the
     purchase history, `:166-168`); customer_index: optional {customer_id str: user_idx}
     (the encoder lookup, `:294-300`); article_ids: optional sequence item_idx -> article id.
+    cold_start: what an unknown user gets -- "error" (the reference: ValueError / an error
+    entry) or "popularity" (opt-in: the unfiltered popular list of the registered
+    "popularity_baseline", under that model name).
     """
 
     def __init__(self, num_users: int, num_items: int, models: Optional[Dict] = None,
                  model_metrics: Optional[Dict[str, Dict[str, float]]] = None,
                  user_history: Optional[Dict[int, set]] = None,
                  customer_index: Optional[Dict[str, int]] = None,
-                 article_ids: Optional[Sequence] = None, device="cuda"):
+                 article_ids: Optional[Sequence] = None, device="cuda",
+                 cold_start: str = "error"):
+        if cold_start not in ("error", "popularity"):
+            raise ValueError('cold_start must be "error" or "popularity"')
+        self.cold_start = cold_start
         self.num_users = num_users
         self.num_items = num_items
         self.device = torch.device(device)
@@ -106,6 +118,18 @@ class Recommender:
         if isinstance(model, NeuralCF) and model._fused():
             model.cache_item_tables()  # a server's weights are fixed: keep the item projection
         self.model_metrics[name] = dict(metrics or {})
+
+    def add_popularity_baseline(self, item_ids, days_ago=None, time_decay: float = 0.0,
+                                window_days: Optional[int] = None) -> PopularityBaseline:
+        """`_load_popularity_baseline` (`serve.py:260-280`): fit a PopularityBaseline on the
+        transactions' item ids (optionally time-decayed / windowed by `days_ago`) and register
+        it as "popularity_baseline".  Non-personalized: `filter_purchased` supplies the
+        history, as for every other model."""
+        model = PopularityBaseline(n_items=self.num_items, k=min(MAX_NUM_ITEMS, self.num_items),
+                                   time_decay=time_decay).to(self.device)
+        model.fit_interactions(item_ids, days_ago=days_ago, window_days=window_days)
+        self.add_model(BASELINE, model)
+        return model
 
     def load_checkpoints(self, checkpoint_dir: str, graph=None) -> List[str]:
         """`_load_models` (`serve.py:170-209`): every `**/*.ckpt`, name = parent dir."""
@@ -154,8 +178,8 @@ class Recommender:
         return None
 
     def _get_best_model(self) -> str:
-        """`serve.py:415-430`: highest 'test_map'; without any, the reference falls back
-        to its popularity baseline (out of scope here) -- we take the first model."""
+        """`serve.py:415-430`: highest 'test_map'; without any, the popularity baseline when
+        one is registered (`:421`), else the first model."""
         best, best_score = None, 0
         for name, m in self.model_metrics.items():
             if "test_map" in m and m["test_map"] > best_score:
@@ -163,8 +187,14 @@ class Recommender:
         if best is None:
             if not self.models:
                 raise ValueError("no model loaded")
-            best = next(iter(self.models))
+            best = BASELINE if BASELINE in self.models else next(iter(self.models))
         return best
+
+    def _cold_start_model(self):
+        if BASELINE not in self.models:
+            raise ValueError('cold_start="popularity" needs a registered "popularity_baseline" '
+                             "(add_popularity_baseline)")
+        return self.models[BASELINE]
 
     def _resolve_model(self, model_name: str):
         if model_name == "best":
@@ -206,9 +236,14 @@ class Recommender:
     def get_recommendations(self, user_id: Union[int, str], model_name: str = "best",
                             num_items: int = 12, filter_purchased: bool = True,
                             include_scores: bool = False) -> Dict:
-        """`serve.py:305-371` (ValueError for an unknown user or model)."""
+        """`serve.py:305-371` (ValueError for an unknown user or model; with
+        cold_start="popularity" an unknown user gets the unfiltered popular list)."""
+        cold = self._cold_start_model() if self.cold_start == "popularity" else None
         uidx = self.get_user_idx(user_id)
         if uidx is None:
+            if cold is not None:
+                vals, items = self._score_batch(cold, [0], num_items, False)
+                return self._result(user_id, BASELINE, vals[0], items[0], include_scores)
             raise ValueError(f"user {user_id} not found")
         name, model = self._resolve_model(model_name)
         vals, items = self._score_batch(model, [uidx], num_items, filter_purchased)
@@ -219,12 +254,17 @@ class Recommender:
                                   filter_purchased: bool = True,
                                   include_scores: bool = False) -> List[Dict]:
         """`serve.py:373-413`, batched: one fused scoring + mask + top-k call for all
-        known users; unknown users get {'user_id', 'error'} in their slot."""
+        known users; unknown users get {'user_id', 'error'} in their slot -- or, with
+        cold_start="popularity", the unfiltered popular list (one more call for all of them)."""
+        cold = self._cold_start_model() if self.cold_start == "popularity" else None
         name, model = self._resolve_model(model_name)
-        idx, slots, results = [], [], []
+        idx, slots, results, cold_slots = [], [], [], []
         for j, uid in enumerate(user_ids):
             u = self.get_user_idx(uid)
-            if u is None:
+            if u is None and cold is not None:
+                results.append(None)
+                cold_slots.append(j)
+            elif u is None:
                 results.append({"user_id": uid, "error": f"user {uid} not found"})
             elif u < 0:  # the reference's embedding lookup raises; its loop records it
                 results.append({"user_id": uid, "error": "index out of range in self"})
@@ -236,4 +276,8 @@ class Recommender:
             vals, items = self._score_batch(model, idx, num_items, filter_purchased)
             for r, j in enumerate(slots):
                 results[j] = self._result(user_ids[j], name, vals[r], items[r], include_scores)
+        if cold_slots:  # the same list for every unknown user: user ids play no part unfiltered
+            vals, items = self._score_batch(cold, [0], num_items, False)
+            for j in cold_slots:
+                results[j] = self._result(user_ids[j], BASELINE, vals[0], items[0], include_scores)
         return results

@@ -647,6 +647,38 @@ hnm_status hnm_rank_metrics_f64(hnm_ctx* ctx, const int64_t* pred, int64_t B, in
                                 const double* inv_log2, double* per_user, int64_t* n_true,
                                 double* sums);
 
+/* ---- PopularityBaseline (src/models/baseline.py) ----------------------------------------
+ * Fit (baseline.py:137-165).  item_ids int64[n]; days_ago int32[n] or NULL; day_weight
+ * f64[num_days] or NULL (= all 1.0).  With cnt[i, d] = the number of rows with item i and
+ * day d:
+ *   count[i] = sum_d cnt[i, d]                                         (int64[num_items])
+ *   pop[i]   = ((0 + cnt[i,0] * w[0]) + cnt[i,1] * w[1]) + ...         (f64[num_items])
+ * in ascending d, each product and each add rounded to float64 once (no fma), so pop is the
+ * same bits on every run and equals that loop on the host.  days_ago == NULL: num_days = 1,
+ * w = {1.0}, pop == count.  Rows whose day is outside [0, num_days) are ignored (the window
+ * of get_popular_items(k, period)); item ids outside [0, num_items) raise the ctx error word
+ * (HNM_EOOB from hnm_ctx_check) and are skipped.  The counts sit in an int32 [slab, num_items]
+ * table in the ctx workspace (integer atomics), folded into pop one ascending slab of days at
+ * a time; slab = 0 picks the slab from a 256 MiB table cap (slab > 0: days per pass, for
+ * tests).  A cell must stay below 2^31 rows.  num_days > 65,536: HNM_EUNSUPPORTED. */
+hnm_status hnm_popularity_fit_f64(hnm_ctx* ctx, const int64_t* item_ids, int64_t n,
+                                  const int32_t* days_ago, const double* day_weight,
+                                  int64_t num_items, int64_t num_days, int64_t slab,
+                                  int64_t* count, double* pop);
+/* Per-user top-K of a popularity order (baseline.py:78-85, 183-187).  order int64[R]: item
+ * ids, most popular first; order_val f32[R]; rank int32[num_items]: position in order, -1 for
+ * items not in it; mask_ptr int64[B+1] / mask_idx int32: the CSR mask of the other top-K
+ * entries (both may be NULL; rows need not be sorted or de-duplicated).  Row b of out_val /
+ * out_idx [B, k] holds the first k entries of order whose item is not in row b of the mask,
+ * in order; slots past the last available entry hold (-inf, -1).  One wave per user over the
+ * window min(R, k + h_b) of the order (h_b = the row's mask length), `chunk` ranks per LDS
+ * bitmap pass (0 = default 8,192; else a multiple of 64 in [64, 8192]).  mask_idx entries
+ * outside [0, num_items) raise the error word.  k = 0 or B = 0: HNM_OK, nothing launched. */
+hnm_status hnm_popularity_topk_f32(hnm_ctx* ctx, const int64_t* order, const float* order_val,
+                                   int64_t R, const int32_t* rank, int64_t num_items,
+                                   const int64_t* mask_ptr, const int32_t* mask_idx, int64_t B,
+                                   int k, int chunk, float* out_val, int64_t* out_idx);
+
 #ifdef __cplusplus
 }
 #endif
