@@ -16,7 +16,8 @@ CSRC = os.path.join(PKG, "csrc")
 BUILD = os.path.join(REPO, "build", "obj")
 LIB = os.path.join(PKG, "libhnm_mi355x.so")
 SOURCES = ["api.hip", "score.hip", "dot_cert.hip", "ncf.hip", "ncf_cert.hip", "ncf_cert_params.hip",
-           "ncf_cert_scan.hip", "ncf_cert_rescore.hip", "ncf_deep.hip", "graph.hip", "widedeep.hip",
+           "ncf_cert_scan.hip", "ncf_cert_rescore.hip", "ncf_deep.hip", "graph.hip", "graph_csr.hip",
+           "graph_plan.hip", "widedeep.hip",
            "widedeep_cert.hip", "widedeep_rescore.hip", "widedeep_features.hip", "eval.hip", "topk_sort.hip", "collective.hip",
            "popularity.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

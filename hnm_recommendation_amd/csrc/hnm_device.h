@@ -35,6 +35,42 @@ __device__ __forceinline__ float wave_max(float x) {
   return x;
 }
 
+// float4 arithmetic of the gather kernels (graph.hip), component by component in x, y, z, w
+// order: f4_fma is four explicit fmaf, f4_add / f4_scale four plain adds / multiplies -- written
+// out so that nothing is left for the compiler to contract or reassociate.  f4_fma and f4_add
+// update their accumulator in place, and float4 operands are taken by reference: member by
+// member, as if written out at the call (a float4 passed by value reached the compiler as a
+// vector and came back as scalar stores in spmm_walk_kernel's epilogue).
+__device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ float4 f4_load(const float* p) {  // 16-B aligned
+  return *reinterpret_cast<const float4*>(p);
+}
+__device__ __forceinline__ void f4_store(float* p, const float4& v) {
+  *reinterpret_cast<float4*>(p) = v;
+}
+__device__ __forceinline__ void f4_fma(float w, const float4& x, float4& acc) {  // acc += w * x
+  acc.x = fmaf(w, x.x, acc.x);
+  acc.y = fmaf(w, x.y, acc.y);
+  acc.z = fmaf(w, x.z, acc.z);
+  acc.w = fmaf(w, x.w, acc.w);
+}
+__device__ __forceinline__ void f4_add(float4& a, const float4& b) {  // a += b
+  a.x += b.x;
+  a.y += b.y;
+  a.z += b.z;
+  a.w += b.w;
+}
+// a += a of lane ^ o: one step of a fixed-order tree across lane groups
+__device__ __forceinline__ void f4_add_xor_lane(float4& a, int o) {
+  a.x += __shfl_xor(a.x, o);
+  a.y += __shfl_xor(a.y, o);
+  a.z += __shfl_xor(a.z, o);
+  a.w += __shfl_xor(a.w, o);
+}
+__device__ __forceinline__ float4 f4_scale(float s, const float4& x) {
+  return make_float4(s * x.x, s * x.y, s * x.z, s * x.w);
+}
+
 __device__ __forceinline__ bool hnm_better(float va, int ia, float vb, int ib) {
   return va > vb || (va == vb && ia < ib);
 }

@@ -1,5 +1,6 @@
-"""LightGCN SpMM plans through the C ABI (graph.hip): the short-row walk, the plan's binding to
-its col / val, and rows_combine's summation order with and without a plan
+"""LightGCN SpMM plans through the C ABI (planning in graph_plan.hip, kernels in graph.hip): the
+short-row walk, the plan's binding to its col / val, and rows_combine's summation order with and
+without a plan
 (reference: lightgcn.py:136-164, `graph @ all_embeddings` per layer)."""
 import ctypes as C
 
@@ -196,7 +197,7 @@ def _raw_graph(N, r, c, v):
 
 @pytest.mark.parametrize("kind", ["small_side_gathers_large", "not_bipartite", "isolated_edges"])
 def test_spmm_bipartite_side_routing(kind):
-    """The plan's bipartite-side detection (graph.hip plan_bipartite_sides) on graphs unlike the
+    """The plan's bipartite-side detection (graph_plan.hip plan_bipartite_sides) on graphs unlike the
     H&M layout: a 3,000-row side whose rows (long AND short) gather a 200,000-row table, so that
     side's short rows join the user-ordered walk; the same graph with two same-side edges (no
     split exists: nothing may move); and isolated rows (self-loop only) on both sides of the
