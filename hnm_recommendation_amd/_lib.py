@@ -333,6 +333,7 @@ HNM_OPT_DEEP_MFMA = 5
 HNM_OPT_LINEAR_MFMA = 6
 HNM_OPT_NCF_TABLES = 7
 HNM_OPT_SCAN_SHAPE = 8
+HNM_OPT_SCAN_PIPE = 9
 
 
 def set_option(device, option, value):

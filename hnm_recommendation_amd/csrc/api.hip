@@ -42,6 +42,7 @@ extern "C" hnm_status hnm_ctx_create(int device, hnm_ctx** out) {
   c->linear_mfma = HNM_LINEAR_MFMA_DEFAULT;
   c->ncf_tables = 1;
   c->scan_shape = 1;
+  c->scan_pipe = 1;
   if (hipMalloc((void**)&c->err_dev, 64) != hipSuccess) {
     free(c);
     hnm_set_error("hnm_ctx_create: hipMalloc of the error word failed");
@@ -123,6 +124,9 @@ extern "C" hnm_status hnm_ctx_set_option(hnm_ctx* ctx, int option, int64_t value
       return HNM_OK;
     case HNM_OPT_SCAN_SHAPE:
       ctx->scan_shape = value != 0;
+      return HNM_OK;
+    case HNM_OPT_SCAN_PIPE:
+      ctx->scan_pipe = value != 0;
       return HNM_OK;
     default:
       hnm_set_error("hnm_ctx_set_option: unknown option %d", option);

@@ -55,10 +55,23 @@ __device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
 // MFMAs (pass_test / dprev below).  Kernel only at the bench shape (tools/scan_ablation.hip,
 // profiles/ncf_scan_issue_ab.txt): 1.710 -> 1.632 ms for the early exit, -> 1.611 ms run late.
 // 168 VGPRs, no scratch (SHAPE 0: 168 and four spilled registers); three waves per SIMD.
-template <int MODE, bool DEEP = false, int SHAPE = 0>
+// PIPE (HNM_OPT_SCAN_PIPE, default 1: the THRESH pass of SHAPE 1): the pair loop pipelined by hand
+// -- a pair's s = 1 operands formed in the gaps of its s = 0 MFMAs, the next pair's s = 0 operands
+// in the gaps of its s = 1 MFMAs, the placement pinned with sched_group_barrier (VALU per gap in
+// the emitted loop: 3 2 3 2 3 2 3 2 | 2 x 8; epilogue 10 ahead, then 3 2 3), the layer-2 block at
+// wave priority 1.  The registers of the look-ahead are ag's (re-loaded per tile behind the pair
+// loop, drained before the prefetch is issued) and those the plain kernel holds across the tile
+// loop for lane-derived addresses and masks (recomputed per tile / in the append path here).
+// Every MFMA keeps its operands and its place in its chain: results bitwise those of PIPE = false,
+// whose code is as it was.  162 VGPRs, no scratch, 50,944 B of LDS (ps has two pad rows), three
+// waves per SIMD.  Kernel only 1.595 -> 1.543 ms, the step 1.811 -> 1.763 ms
+// (profiles/ncf_scan_pipe_ab.txt: the priority alone on the plain loop 1.558, the pipelined loop
+// alone 1.577).
+template <int MODE, bool DEEP = false, int SHAPE = 0, bool PIPE = false>
 __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kernel(ScanArgs A) {
   constexpr bool S16 = SHAPE == 1;  // layer 2 and the GMF on v_mfma_f32_16x16x32_f16
   static_assert(!(S16 && DEEP), "the deep scan has the 32x32x16 layout only");
+  static_assert(!PIPE || (S16 && MODE == SCAN_THRESH), "the pipelined pair loop: THRESH, layout 1");
   // LDS row stride in halfs: 144 B (conflict-free b128 reads of the 32x32x16 operands: lane
   // (j, h) reads row j) / S16: 128 B with the row's 16-B chunks XOR-swizzled (s16_chunk)
   constexpr int RS = S16 ? 64 : 72;
@@ -70,7 +83,9 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
   if (MODE == SCAN_SAMPLE && A.gate && *A.gate == 0) return;  // whole grid: gated off
   __shared__ __attribute__((aligned(16))) _Float16 qs[2][TILE * RS];  // double-buffered tiles
   __shared__ __attribute__((aligned(16))) _Float16 gs[2][TILE * RS];
-  __shared__ __attribute__((aligned(16))) _Float16 ps[NU * 64];
+  // PIPE: two more rows, which the look-ahead reads of a block's last pair may touch
+  constexpr int PSR = NU + (PIPE ? 2 : 0);
+  __shared__ __attribute__((aligned(16))) _Float16 ps[PSR * 64];
   // per wave: the GMF table of its 32 users x the tile's 32 items (FOLD: folded test terms,
   // pair-interleaved: g7 index below; DEBUG: gsm[row][item])
   __shared__ __attribute__((aligned(16))) float gsm[4][32][33];
@@ -91,7 +106,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
   const int part_start = p * (int)A.ipp;
   const int part_end = std::min<int>((int)A.I, part_start + (int)A.ipp);
 
-  for (int e = tid; e < NU * 8; e += 256) {
+  for (int e = tid; e < PSR * 8; e += 256) {
     const int r = e >> 3, c = e & 7;
     h8 v = {};
     if (ublk + r < A.B) v = *reinterpret_cast<const h8*>(A.P16 + (ublk + r) * 64 + 8 * c);
@@ -271,8 +286,11 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
     const float bj = nb, dj = nd;  // bound terms of this tile's item j (test units)
     // the prefetch is the only global load in the tile body (vmcnt waits are in order: any
     // later load's wait would also wait for it)
+    // PIPE: ag, re-loaded behind the previous tile's pair loop, is drained first for that reason
+    if constexpr (PIPE) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     if (tn < ntiles) fetch(part_start + tn * TILE);
-    int lrow;  // lane (j, h)'s operand row offset in the tile buffers (recomputed: see srow_of)
+    int lrow = 0;  // lane (j, h)'s operand row offset in the tile buffers (recomputed: see srow_of)
+    if constexpr (!PIPE)  // (layout 1 reads by so0 / so1; PIPE has no registers for its inputs)
     asm volatile("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(lrow) : "v"(j), "v"(RS), "v"(8 * h));
 
     // S16: lane (c16, g4)'s operand offsets in the tile buffers at k-steps 0 and 1, item half 0
@@ -281,9 +299,17 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
     // in bit 0, and the rows' swizzles (0, 1, 6, 7 against 2, 3, 4, 5 on either row parity) keep
     // the sixteen 16-B slots of the 256-B bank row distinct.  Recomputed per tile as lrow is.
     int so0 = 0, so1 = 0;
+    // PIPE: the GMF table's store addresses come from this per-tile copy of the lane index too
+    // (one base and immediate offsets; from `lane` they are eight registers held across the tile
+    // loop, which the pipelined pair loop has not got)
+    int c16t = c16, g4t = g4;
     if constexpr (S16) {
       int ln;
       asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+      if constexpr (PIPE) {
+        c16t = ln & 15;
+        g4t = ln >> 4;
+      }
       const int x0 = (ln >> 4) ^ ((ln >> 1) & 7);
       so0 = (ln & 15) * RS + 8 * x0;
       so1 = (ln & 15) * RS + 8 * (x0 ^ 4);
@@ -308,19 +334,24 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
       if (MODE != SCAN_DEBUG) {
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
+          if constexpr (PIPE) {  // __shfl without its own copy of the lane index
+            bjn[n] = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * (c16t + 16 * n), __float_as_int(bj)));
+            djn[n] = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * (c16t + 16 * n), __float_as_int(dj)));
+          } else {
           bjn[n] = __shfl(bj, c16 + 16 * n);
           djn[n] = __shfl(dj, c16 + 16 * n);
+          }
         }
       }
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = 16 * m + 4 * g4 + r;
+          const int row = 16 * m + 4 * g4t + r;
           const float2 tc = ut[wave][row];
 #pragma unroll
           for (int n = 0; n < 2; ++n)
-            g7[(((row >> 1) * 16 + c16) << 2) + ((row & 1) << 1) + n] =
+            g7[(((row >> 1) * 16 + c16t) << 2) + ((row & 1) << 1) + n] =
                 MODE == SCAN_DEBUG ? ga[m][n][r] * cg
                                    : (ga[m][n][r] * cg + sgn * fmaf(tc.y, djn[n], bjn[n])) - tc.x;
         }
@@ -406,6 +437,28 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         // re-scoring's best-first order, the test value -- at the slot the pair's rank in the
         // pass mask gives (no cross-lane moves; the store addresses are uniform bases)
         const int ca = hnm_readlane_i(ccount, ua), cb = hnm_readlane_i(ccount, ub);
+        if constexpr (PIPE) {
+        // the appends below word for word, on a copy of the lane index made here: what they
+        // derive from it (masks, item ids, the lanes of users a and b) is then computed in this
+        // rare path, not held in registers across the pair loop
+        int pl;
+        asm volatile("v_mov_b32 %0, %1" : "=v"(pl) : "v"(lane));
+        if (pl < 16) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int uu = r >> 1, it = pl + 16 * (r & 1);
+            const unsigned mu = (unsigned)(m >> (32 * uu));
+            const int ps = (uu ? cb : ca) + __builtin_popcount(mu & ((1u << it) - 1u));
+            if (((mu >> it) & 1u) && ps < A.capp) {
+              const int so = (uu ? ub : ua) * (int)segstride * 4;
+              __builtin_amdgcn_raw_buffer_store_b32((int)(base + it), segrs, ps * 4, so, 0);
+              __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(d[r]), segdrs, ps * 4, so, 0);
+            }
+          }
+        }
+        if (pl == ua) ccount += __builtin_popcount((unsigned)m);
+        if (pl == ub && hasb) ccount += __builtin_popcount((unsigned)(m >> 32));
+        } else {
         if (lane < 16) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -423,12 +476,141 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         }
         if (lane == ua) ccount += __builtin_popcount((unsigned)m);
         if (lane == ub && hasb) ccount += __builtin_popcount((unsigned)(m >> 32));
+        }  // !PIPE
       }
     };
     // The test of a pair runs one iteration late, among the next pair's layer-2 MFMAs (and after
     // the loop for the last pair): placed behind the pair's own epilogue it waited for the last
     // MFMA of the chain and then held the wave's next LDS reads back by its compares and scalar
     // tail.  The seed of the first iteration passes nothing.
+    if constexpr (PIPE) {
+      // The pair loop pipelined by hand (HNM_OPT_SCAN_PIPE): the same 20 MFMAs on the same
+      // operands in the same chains, the B operands formed one k-step ahead so that the packed
+      // adds sit two (three with a compare) to an MFMA gap instead of in front of the MFMAs.
+      //   head          ds_read: pair k + 1's s = 0 fragments
+      //   s = 0 MFMAs   form pair k's s = 1 operands; the compares of pair k - 1
+      //   s = 1 MFMAs   form pair k + 1's s = 0 operands (the tile's last pair: from rows past
+      //                 nu -- zeros, another wave's users or the two pad rows of ps -- and unused)
+      //   epilogue      ds_read: pair k's seeds and pair k + 1's s = 1 fragments (into the
+      //                 registers of pair k's: read at the head they cost eight register copies a
+      //                 pair, and with the seeds there the tile prefetch spilled); ten converts,
+      //                 then two under each of the first three MFMAs
+      // ag's registers carry the look-ahead: it is re-loaded behind the loop for the next tile.
+      auto ldp = [&](const int r, const int s) {
+        return *reinterpret_cast<const h8*>(&pw[r * 64 + 32 * s]);
+      };
+      auto form = [](const h8 pf, const h8 qf) {
+        const h8 x = pf + qf;
+        return __builtin_elementwise_min(__builtin_elementwise_max(x, (h8){}), (h8)(_Float16)1.f);
+      };
+#define HNM_SGB(M, N) __builtin_amdgcn_sched_group_barrier(M, N, 0);
+#define HNM_SGB_MFMA_VALU(NV) HNM_SGB(0x008, 1) HNM_SGB(0x002, NV)
+      h8 xa[2], xb[2];  // the pair's s = 0 B operands [item half n], users a and b
+      h8 pa1, pb1;      // its s = 1 fragments
+      {
+        const h8 pa0 = ldp(0, 0), pb0 = ldp(1, 0);
+        pa1 = ldp(0, 1);
+        pb1 = ldp(1, 1);
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          xa[n] = form(pa0, q[2 * n]);
+          xb[n] = form(pb0, q[2 * n]);
+        }
+      }
+      f32x4 dprev = {-1.f, -1.f, -1.f, -1.f};
+      for (int u = 0; u < nu; u += 2) {
+        // the wave issues its layer-2 block ahead of waves in their epilogue or append path
+        // (kernel only 1.577 -> 1.556 ms: profiles/ncf_scan_pipe_ab.txt); 0 again at the epilogue
+        __builtin_amdgcn_s_setprio(1);
+        const h8 na0 = ldp(u + 2, 0), nb0 = ldp(u + 3, 0);
+        f32x4 ca[2][2], cb[2][2];  // [unit half m][item half n], users a and b
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+          for (int m = 0; m < 2; ++m) {
+            ca[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aw[2 * m], xa[n], b2q[m], 0, 0, 0);
+            cb[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aw[2 * m], xb[n], b2q[m], 0, 0, 0);
+          }
+        h8 x1a[2], x1b[2];
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          x1a[n] = form(pa1, q[2 * n + 1]);
+          x1b[n] = form(pb1, q[2 * n + 1]);
+        }
+        // pass_test's four compares, named here too: in program order they then stand among the
+        // formation above, and the group barriers below take them into the first eight gaps
+        // (pass_test's own fold into these)
+        const uint64_t early = __ballot(!(dprev[0] < 0.f)) | __ballot(!(dprev[1] < 0.f)) |
+                               __ballot(!(dprev[2] < 0.f)) | __ballot(!(dprev[3] < 0.f));
+        asm volatile("" ::"s"(early));
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+          for (int m = 0; m < 2; ++m) {
+            ca[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aw[2 * m + 1], x1a[n], ca[m][n], 0, 0, 0);
+            cb[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aw[2 * m + 1], x1b[n], cb[m][n], 0, 0, 0);
+          }
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          xa[n] = form(na0, q[2 * n]);
+          xb[n] = form(nb0, q[2 * n]);
+          // formed here, under these MFMAs: unpinned they sink behind the early-exit branch
+          asm volatile("" : "+v"(xa[n]), "+v"(xb[n]));
+        }
+        HNM_SGB(0x100, 2)
+        HNM_SGB_MFMA_VALU(3) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(3) HNM_SGB_MFMA_VALU(2)
+        HNM_SGB_MFMA_VALU(3) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(3) HNM_SGB_MFMA_VALU(2)
+        HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2)
+        HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2)
+        pass_test(dprev, u - 2);  // the pair before this one
+        __builtin_amdgcn_s_setprio(0);
+        // lanes 0-15: (a, c), (a, c + 16), (b, c), (b, c + 16); other lanes' rows are unused
+        f32x4 d = *reinterpret_cast<const f32x4*>(&g7[((u >> 1) * 16 + (lane & 15)) << 2]);
+        pa1 = ldp(u + 2, 1);
+        pb1 = ldp(u + 3, 1);
+        h8 ya[2], yb[2];  // [item half n], the accumulators m = 0, 1 of the half as one h8
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          ya[0][e] = (_Float16)ca[e >> 2][0][e & 3];
+          ya[1][e] = (_Float16)ca[e >> 2][1][e & 3];
+          yb[0][e] = (_Float16)cb[e >> 2][0][e & 3];
+          yb[1][e] = (_Float16)cb[e >> 2][1][e & 3];
+        }
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          ya[f] = __builtin_elementwise_min(__builtin_elementwise_max(ya[f], (h8){}), (h8)(_Float16)1.f);
+          yb[f] = __builtin_elementwise_min(__builtin_elementwise_max(yb[f], (h8){}), (h8)(_Float16)1.f);
+        }
+        d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewa[0], ya[0], d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewa[1], ya[1], d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewb[0], yb[0], d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewb[1], yb[1], d, 0, 0, 0);
+        HNM_SGB(0x100, 3)
+        HNM_SGB(0x002, 10)
+        HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2)
+        HNM_SGB(0x008, 1)
+        dprev = d;  // tested in the next iteration
+      }
+#undef HNM_SGB_MFMA_VALU
+#undef HNM_SGB
+      // the next tile's GMF A operand: issued here, drained at the top of the tile before its
+      // prefetch is issued (the lane index goes through an asm so that the loads stay here)
+      {
+        int ln;
+        asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            const int ur = 16 * m + (ln & 15);
+            h8 z = {};
+            ag[2 * m + s] =
+                ur < nu ? *reinterpret_cast<const h8*>(A.WG16 + (u0 + ur) * 64 + 32 * s + 8 * (ln >> 4))
+                        : z;
+          }
+      }
+      pass_test(dprev, (nu - 1) & ~1);  // the tile's last pair
+    } else {
     f32x4 dprev = {-1.f, -1.f, -1.f, -1.f};
     for (int u = 0; u < nu; u += 2) {
       // user b = u + 1 even past nu (zero P~ rows; FOLD: folded term -inf / not stored)
@@ -573,6 +755,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
       }
     }
     if constexpr (MODE == SCAN_THRESH) pass_test(dprev, (nu - 1) & ~1);  // the tile's last pair
+    }  // !PIPE
     }  // nu > 0
     if (tn < ntiles) stash(cur ^ 1);
     __syncthreads();
@@ -587,6 +770,10 @@ void launch_scan(hnm_ctx* ctx, dim3 grid, const ScanArgs& a) {
   // scan has the 32x32x16 layout only)
   if (a.W3h)
     hipLaunchKernelGGL((ncf16_scan_kernel<MODE, true>), grid, dim3(256), 0, ctx->stream, a);
+  else if (ctx->scan_shape && ctx->scan_pipe && MODE == SCAN_THRESH)
+    // HNM_OPT_SCAN_PIPE: the threshold pass of layout 1 with its pair loop pipelined by hand
+    hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, 1, true>), grid, dim3(256), 0,
+                       ctx->stream, a);
   else if (ctx->scan_shape)
     hipLaunchKernelGGL((ncf16_scan_kernel<MODE, false, 1>), grid, dim3(256), 0, ctx->stream, a);
   else

@@ -108,6 +108,13 @@ enum { HNM_OPT_PREFILTER = 1,
  * the same certified bound, so every returned id and score is bitwise the same (the A/B and
  * parity switch); the deep towers' scan ignores it. */
 #define HNM_OPT_SCAN_SHAPE 8
+/* NeuralCF certified top-K, two-layer towers on the 16x16x32 layout (HNM_OPT_SCAN_SHAPE 1): the
+ * threshold pass of the f16 scan runs its user-pair loop software-pipelined by hand -- the next
+ * pair's P~ reads and B operands formed under this pair's layer-2 MFMAs, that block at a raised
+ * wave priority -- (1, default) or as the compiler schedules the plain loop (0).  The same MFMAs on the same operands in the same chains, so every
+ * returned id and score is bitwise the same (the A/B and parity switch); layout 0 and the deep
+ * towers' scan ignore it. */
+#define HNM_OPT_SCAN_PIPE 9
 hnm_status hnm_ctx_set_option(hnm_ctx* ctx, int option, int64_t value);
 /* Pre-filter counters since the last reset (counted only while HNM_OPT_STATS is 1): out[0]
  * rows scored, out[1] candidates re-scored in fp32, out[2] rows that took the exact fallback
