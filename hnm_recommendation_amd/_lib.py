@@ -334,6 +334,7 @@ HNM_OPT_LINEAR_MFMA = 6
 HNM_OPT_NCF_TABLES = 7
 HNM_OPT_SCAN_SHAPE = 8
 HNM_OPT_SCAN_PIPE = 9
+HNM_OPT_SCAN_SPARSE = 10
 
 
 def set_option(device, option, value):

@@ -34,6 +34,7 @@ struct hnm_ctx {
   int ncf_tables;                  // HNM_OPT_NCF_TABLES (default 1)
   int scan_shape;                  // HNM_OPT_SCAN_SHAPE (default 1)
   int scan_pipe;                   // HNM_OPT_SCAN_PIPE (default 1)
+  int scan_sparse;                 // HNM_OPT_SCAN_SPARSE (default 1)
   void* comm;                      // RCCL communicator (ncclComm_t) of the C-side exchange
   int comm_owned;                  // 1: created by hnm_ctx_rccl_init, destroyed with the ctx
   unsigned long long* stats_dev;   // pre-filter counters: rows, candidates, fallback rows,

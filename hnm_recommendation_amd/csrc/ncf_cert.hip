@@ -35,7 +35,11 @@
 // (HNM_OPT_SCAN_SHAPE: 1 = layer 2 and the GMF on v_mfma_f32_16x16x32_f16, the default; 0 = on
 // v_mfma_f32_32x32x16_f16; the A/B and parity switch) satisfy (*) with the same e(u, i); their
 // approximate scores may differ in the last bits, the returned top-K never does
-// (tests/test_gpu_ncf_scan_shape.py).
+// (tests/test_gpu_ncf_scan_shape.py).  Layout 1 has a third summation order: its epilogue's 32
+// unit terms summed by 2 v_smfmac_f32_16x16x64_f16 (HNM_OPT_SCAN_SPARSE 1, the default) in place
+// of 4 dense instructions (0).  The sparse instruction keeps f16 denormals and accumulates exact
+// products in fp32 as the dense ones do (tools/mfma_semantics_probe.hip (d)), so it satisfies (*)
+// with the same e(u, i) (tests/test_gpu_ncf_scan_sparse.py checks it pair by pair).
 //
 // Scaling: every f16 operand is scaled by a power of two so its magnitude is <= 1 (layer-1
 // inputs <= 0.5, which also makes the packed add's [0,1] CLAMP an exact ReLU:

@@ -11,6 +11,24 @@ __device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
+// SPARSE: the B operand of item half n, the converted and clamped accumulators m = 0, 1 of users a
+// and b interleaved a dword at a time (element 4 q + i = user a's converted value e = 2 q + i,
+// 4 q + 2 + i = user b's; e as in the dense epilogue's h8: unit 16 (e >> 2) + 4 (lane >> 4) + (e & 3))
+typedef _Float16 h16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ h16 sparse_b(const f32x4 (&ca)[2][2], const f32x4 (&cb)[2][2], const int n) {
+  // as two h8 whose clamp folds into the packed converts (on an h16 it does not), then a register
+  // renaming
+  h8 ya, yb;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    ya[e] = (_Float16)ca[e >> 2][n][e & 3];
+    yb[e] = (_Float16)cb[e >> 2][n][e & 3];
+  }
+  ya = __builtin_elementwise_min(__builtin_elementwise_max(ya, (h8){}), (h8)(_Float16)1.f);
+  yb = __builtin_elementwise_min(__builtin_elementwise_max(yb, (h8){}), (h8)(_Float16)1.f);
+  return __builtin_shufflevector(ya, yb, 0, 1, 8, 9, 2, 3, 10, 11, 4, 5, 12, 13, 6, 7, 14, 15);
+}
+
 // A wave owns 32 users, a workgroup 128; 32-item tiles of Q16/G16 go through LDS.
 // Per (user pair, tile): layer 2 as 4 + 4 v_mfma_f32_32x32x16_f16 (two independent chains;
 // A = W2~, B = clamp(P~ + Q~) built with 16 packed adds per user; v_mfma_f32_32x32x16_f16 B
@@ -67,11 +85,30 @@ __device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
 // waves per SIMD.  Kernel only 1.595 -> 1.543 ms, the step 1.811 -> 1.763 ms
 // (profiles/ncf_scan_pipe_ab.txt: the priority alone on the plain loop 1.558, the pipelined loop
 // alone 1.577).
-template <int MODE, bool DEEP = false, int SHAPE = 0, bool PIPE = false>
+// SPARSE (HNM_OPT_SCAN_SPARSE, every pass of SHAPE 1 that runs the matrix epilogue): wm . relu(H~)
+// as 2 v_smfmac_f32_16x16x64_f16, one per item half n, in place of the 4 dense instructions whose
+// A operands carry one non-zero row of 16.  The sparse instruction takes a dense B of K = 64 (16
+// halves a lane) and an A with two stored values for every four of k, their positions in 2-bit
+// fields of an index register (tools/mfma_semantics_probe.hip (d): lane (row, ga)'s stored pair t
+// meets elements 4 q .. 4 q + 3 of the B lanes of k-group 2 (ga & 1) + (t >> 1), q = 2 (ga >> 1) +
+// (t & 1); the field of a pair is p0 | p1 << 2; D as the dense 16x16 one).  B of half n interleaves
+// the converted accumulators of users a and b a dword at a time -- a a b b a a b b along every
+// lane's 16 halves, each dword the packed convert + clamp it was -- so row n (user a) stores wm at
+// positions {0, 1} of every group and row 2 + n (user b) at {2, 3}: exact 2:4, and a row never
+// meets the other user's values.  The two instructions chain on the folded seeds and leave the 64
+// test values where the four left them.  The products and their fp32 accumulation are those of
+// the dense epilogue in another order, which (*) allows (the header of ncf_cert.hip: the third
+// summation order of the scan, after the two layouts').  The instruction takes the dense 16x16x32's
+// 16 cycles, so an iteration's matrix-pipe time falls from 20 to 18 of them.  152 VGPRs, no scratch,
+// 50,944 B of LDS, three waves per SIMD; converts in the emitted loop 10 ahead, 6 under the first
+// instruction.  Kernel only 1.667 -> 1.626 ms, the step 1.833 -> 1.786 ms; matrix-pipe busy cycles
+// -9.7 %, the launch's cycles -3.0 % at an unchanged clock (profiles/ncf_scan_sparse_ab.txt).
+template <int MODE, bool DEEP = false, int SHAPE = 0, bool PIPE = false, bool SPARSE = false>
 __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kernel(ScanArgs A) {
   constexpr bool S16 = SHAPE == 1;  // layer 2 and the GMF on v_mfma_f32_16x16x32_f16
   static_assert(!(S16 && DEEP), "the deep scan has the 32x32x16 layout only");
   static_assert(!PIPE || (S16 && MODE == SCAN_THRESH), "the pipelined pair loop: THRESH, layout 1");
+  static_assert(!SPARSE || S16, "the sparse epilogue: layout 1");
   // LDS row stride in halfs: 144 B (conflict-free b128 reads of the 32x32x16 operands: lane
   // (j, h) reads row j) / S16: 128 B with the row's 16-B chunks XOR-swizzled (s16_chunk)
   constexpr int RS = S16 ? 64 : 72;
@@ -148,6 +185,8 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
   }
   // epilogue A operands (16x16x32: lane holds A[row lane & 15][k = 8 (lane >> 4) + e])
   h8 ewa[2], ewb[2];
+  h8 ews[2];     // SPARSE: stored A values [item half n], wm in rows n (user a) and 2 + n (user b)
+  int ewi = 0;   // SPARSE: their positions, {0, 1} in user a's rows and {2, 3} in user b's
   h2 wm2[8];  // DEBUG: wm of this lane's accumulator rows, in pairs
   h8 e3[2][2];  // DEEP: layer-3 A operands [item half g][accumulator half f]
   h4 ep[4];     // DEEP: prediction A operands, wp3 in row idx = 2 user + g
@@ -167,6 +206,19 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
       for (int e = 0; e < 4; ++e) ep[idx][e] = m == idx ? A.wph[4 * kg + e] : (_Float16)0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) b3c[r] = A.b3s[4 * kg + r];
+  } else if constexpr (SPARSE) {
+    // stored value f of lane (c16, g4): pair t = f >> 1 meets dword q = 2 (g4 >> 1) + (t & 1) of
+    // its user in the B lanes of k-group gb = 2 (g4 & 1) + (t >> 1), i.e. that lane's converted
+    // accumulator e = 2 q + (f & 1): unit 16 (e >> 2) + 4 gb + (e & 3)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int f = 0; f < 8; ++f) {
+        const int t = f >> 1, gb = 2 * (g4 & 1) + (t >> 1), e = 2 * (2 * (g4 >> 1) + (t & 1)) + (f & 1);
+        const _Float16 wv = A.wmh[16 * (e >> 2) + 4 * gb + (e & 3)];
+        ews[n][f] = (c16 == n || c16 == 2 + n) ? wv : (_Float16)0.f;
+      }
+    ewi = (c16 & 2) ? 0xEEEE : 0x4444;
   } else if constexpr (S16) {
     // the B operand of (user, item half n) is the lane's converted accumulators m = 0, 1 as one
     // h8: k = 8 g4 + e is unit 16 (e >> 2) + 4 g4 + (e & 3); A row 2 user + n holds wm in that
@@ -568,6 +620,16 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         f32x4 d = *reinterpret_cast<const f32x4*>(&g7[((u >> 1) * 16 + (lane & 15)) << 2]);
         pa1 = ldp(u + 2, 1);
         pb1 = ldp(u + 3, 1);
+        if constexpr (SPARSE) {
+          // the 16 converts as they were, into the interleaved operands; half 0's eight and two of
+          // half 1's ahead of the first instruction, the rest under it
+          d = __builtin_amdgcn_smfmac_f32_16x16x64_f16(ews[0], sparse_b(ca, cb, 0), d, ewi, 0, 0);
+          d = __builtin_amdgcn_smfmac_f32_16x16x64_f16(ews[1], sparse_b(ca, cb, 1), d, ewi, 0, 0);
+          HNM_SGB(0x100, 3)
+          HNM_SGB(0x002, 10)
+          HNM_SGB_MFMA_VALU(6)
+          HNM_SGB(0x008, 1)
+        } else {
         h8 ya[2], yb[2];  // [item half n], the accumulators m = 0, 1 of the half as one h8
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -589,6 +651,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         HNM_SGB(0x002, 10)
         HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2)
         HNM_SGB(0x008, 1)
+        }  // !SPARSE
         dprev = d;  // tested in the next iteration
       }
 #undef HNM_SGB_MFMA_VALU
@@ -691,6 +754,9 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
               z = __builtin_elementwise_min(__builtin_elementwise_max(z, (h4){}), (h4)(_Float16)1.f);
               d = __builtin_amdgcn_mfma_f32_16x16x16f16(ep[2 * uu + g], z, d, 0, 0, 0);
             }
+        } else if constexpr (SPARSE) {
+          d = __builtin_amdgcn_smfmac_f32_16x16x64_f16(ews[0], sparse_b(ca, cb, 0), d, ewi, 0, 0);
+          d = __builtin_amdgcn_smfmac_f32_16x16x64_f16(ews[1], sparse_b(ca, cb, 1), d, ewi, 0, 0);
         } else {
           d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewa[0], ya[0], d, 0, 0, 0);
           d = __builtin_amdgcn_mfma_f32_16x16x32_f16(ewa[1], ya[1], d, 0, 0, 0);
@@ -770,9 +836,17 @@ void launch_scan(hnm_ctx* ctx, dim3 grid, const ScanArgs& a) {
   // scan has the 32x32x16 layout only)
   if (a.W3h)
     hipLaunchKernelGGL((ncf16_scan_kernel<MODE, true>), grid, dim3(256), 0, ctx->stream, a);
-  else if (ctx->scan_shape && ctx->scan_pipe && MODE == SCAN_THRESH)
+  else if (ctx->scan_shape && ctx->scan_pipe && MODE == SCAN_THRESH) {
     // HNM_OPT_SCAN_PIPE: the threshold pass of layout 1 with its pair loop pipelined by hand
-    hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, 1, true>), grid, dim3(256), 0,
+    // (HNM_OPT_SCAN_SPARSE: every pass of layout 1 with the epilogue on the sparse instruction)
+    if (ctx->scan_sparse)
+      hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, 1, true, true>), grid, dim3(256), 0,
+                         ctx->stream, a);
+    else
+      hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, 1, true>), grid, dim3(256), 0,
+                         ctx->stream, a);
+  } else if (ctx->scan_shape && ctx->scan_sparse)
+    hipLaunchKernelGGL((ncf16_scan_kernel<MODE, false, 1, false, true>), grid, dim3(256), 0,
                        ctx->stream, a);
   else if (ctx->scan_shape)
     hipLaunchKernelGGL((ncf16_scan_kernel<MODE, false, 1>), grid, dim3(256), 0, ctx->stream, a);

@@ -115,6 +115,15 @@ enum { HNM_OPT_PREFILTER = 1,
  * returned id and score is bitwise the same (the A/B and parity switch); layout 0 and the deep
  * towers' scan ignore it. */
 #define HNM_OPT_SCAN_PIPE 9
+/* NeuralCF certified top-K, two-layer towers on the 16x16x32 layout (HNM_OPT_SCAN_SHAPE 1): the
+ * f16 scan's epilogue wm . relu(H~) runs as 2 v_smfmac_f32_16x16x64_f16 a user pair and tile --
+ * the converted accumulators of the pair's two users interleaved into one B operand of K = 64, wm
+ * as an A operand with exact 2:4 structured sparsity -- (1, default) or as the 4 dense
+ * v_mfma_f32_16x16x32_f16 (0).  The same products accumulated in fp32 in another order,
+ * within the same certified bound, so every returned id and score is bitwise the same (the A/B
+ * and parity switch); candidate counts may differ by a test value next to a threshold.  Layout 0
+ * and the deep towers' scan ignore it. */
+#define HNM_OPT_SCAN_SPARSE 10
 hnm_status hnm_ctx_set_option(hnm_ctx* ctx, int option, int64_t value);
 /* Pre-filter counters since the last reset (counted only while HNM_OPT_STATS is 1): out[0]
  * rows scored, out[1] candidates re-scored in fp32, out[2] rows that took the exact fallback

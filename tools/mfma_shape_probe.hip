@@ -6,12 +6,19 @@
 // v_mfma_f32_16x16x32_f16 (four chains).  Question: does the 16x16x32 shape buy clock under
 // the power limit (MI355X_MICROARCH.md: ~1.15x FLOP/s in bare bf16 loops)?
 // Round 6: SHAPE 2 / 3, the block-scaled e4m3 32x32x64 (bare / with the scan's operand work).
+// COST (the sparse wm epilogue's premise): v_smfmac_f32_16x16x64_f16 (A 2:4 sparse, B of K = 64)
+// beside v_mfma_f32_16x16x32_f16 with nothing else in the loop, at the same occupancy: time per
+// instruction and SIMD, issued on four accumulators in turn and chained on one, on random
+// operands and with the epilogue's A pattern (rows 0-3 of 16 non-zero).
 // Build: hipcc --offload-arch=gfx950 -O3 tools/mfma_shape_probe.hip -o tools/bin/mfma_shape_probe
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
+
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h16 __attribute__((ext_vector_type(16)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef short s2 __attribute__((ext_vector_type(2)));
 typedef int i8v __attribute__((ext_vector_type(8)));
@@ -123,6 +130,69 @@ __global__ __launch_bounds__(256, 3) void probe(const h8* __restrict__ in, float
   if (blockIdx.x == 0 && threadIdx.x == 0) *cyc = t1 - t0;
 }
 
+// SPARSE: v_smfmac_f32_16x16x64_f16, else v_mfma_f32_16x16x32_f16; CHAIN: 16 instructions an
+// iteration on one accumulator, else on four in turn; rows4: A zeroed outside rows 0-3
+template <bool SPARSE, bool CHAIN>
+__global__ __launch_bounds__(256, 3) void cost(const h8* __restrict__ in, float* __restrict__ out, int iters,
+                                               int rows4) {
+  const int lane = threadIdx.x & 63;
+  h8 a[4];
+  h16 b[4];
+  int idx[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    a[s] = in[(s * 64 + lane + blockIdx.x * 7) & 4095];
+    if (rows4 && (lane & 15) >= 4) a[s] = (h8){};
+    const h8 lo = in[(s * 64 + lane + 2048 + blockIdx.x * 13) & 4095];
+    const h8 hi = in[(s * 64 + lane + 1024 + blockIdx.x * 11) & 4095];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      b[s][e] = lo[e];
+      b[s][8 + e] = hi[e];
+    }
+    idx[s] = ((lane + s) & 1) ? 0xEEEE : 0x4444;  // positions {2, 3} / {0, 1}
+  }
+  f32x4 c[4] = {};
+  for (int it = 0; it < iters; ++it) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        f32x4& acc = c[CHAIN ? 0 : s];
+        if (SPARSE) acc = __builtin_amdgcn_smfmac_f32_16x16x64_f16(a[s], b[(s + r) & 3], acc, idx[s], 0, 0);
+        else acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[s], *reinterpret_cast<const h8*>(&b[(s + r) & 3]), acc, 0, 0, 0);
+      }
+  }
+  float keep = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) keep += c[0][r] + c[1][r] + c[2][r] + c[3][r];
+  out[blockIdx.x * 256 + threadIdx.x] = keep;
+}
+
+template <bool SPARSE, bool CHAIN>
+static float run_cost(const h8* in, float* out, int blocks, int iters, int rows4) {
+  hipLaunchKernelGGL((cost<SPARSE, CHAIN>), dim3(blocks), dim3(256), 0, 0, in, out, iters, rows4);
+  (void)hipDeviceSynchronize();
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0);
+  (void)hipEventCreate(&e1);
+  float best = 1e30f;
+  for (int rep = 0; rep < 5; ++rep) {
+    (void)hipEventRecord(e0);
+    hipLaunchKernelGGL((cost<SPARSE, CHAIN>), dim3(blocks), dim3(256), 0, 0, in, out, iters, rows4);
+    (void)hipEventRecord(e1);
+    (void)hipEventSynchronize(e1);
+    float ms;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    if (ms < best) best = ms;
+  }
+  // three waves a SIMD, 16 instructions an iteration each
+  printf("cost %-15s %-5s %-6s %8.3f ms  %6.2f ns an instruction and SIMD\n",
+         SPARSE ? "smfmac 16x16x64" : "mfma 16x16x32", CHAIN ? "chain" : "4 acc", rows4 ? "rows4" : "random", best,
+         best * 1e6 / ((double)iters * 16 * 3));
+  return best;
+}
+
 template <int SHAPE>
 static void run(const h8* in, float* out, long long* cyc, int blocks, int iters, const char* name) {
   hipLaunchKernelGGL(probe<SHAPE>, dim3(blocks), dim3(256), 0, 0, in, out, iters, cyc);
@@ -175,6 +245,20 @@ int main(int argc, char** argv) {
     run<1>(in, out, cyc, blocks, iters, "16x16x32");
     run<2>(in, out, cyc, blocks, iters, "e4m3 bare");
     run<3>(in, out, cyc, blocks, iters, "e4m3 +ops");
+  }
+  // seven alternating rounds a pattern (each time the best of 5 launches); the verdict is the ratio
+  // of the bests and of the medians
+  for (int rows4 = 0; rows4 < 2; ++rows4) {
+    float t[4][7];
+    for (int rep = 0; rep < 7; ++rep) {
+      t[0][rep] = run_cost<false, false>(in, out, blocks, iters, rows4);
+      t[1][rep] = run_cost<true, false>(in, out, blocks, iters, rows4);
+      t[2][rep] = run_cost<false, true>(in, out, blocks, iters, rows4);
+      t[3][rep] = run_cost<true, true>(in, out, blocks, iters, rows4);
+    }
+    for (int c = 0; c < 4; ++c) std::sort(t[c], t[c] + 7);
+    printf("cost sparse / dense, %s: 4 acc best %.3f median %.3f, chain best %.3f median %.3f\n",
+           rows4 ? "rows4" : "random", t[1][0] / t[0][0], t[1][3] / t[0][3], t[3][0] / t[2][0], t[3][3] / t[2][3]);
   }
   return 0;
 }

@@ -2,7 +2,8 @@
 // (B = 4096 users x 105,542 items, 24 partitions): kernel-only time, best of 7 after a
 // clock warm-up, so scan variants can be compared without the rest of the step.  Both layouts
 // of the two-layer scan are timed, alternating (SHAPE 0: 32x32x16, 1: 16x16x32;
-// HNM_OPT_SCAN_SHAPE), and layout 1 with its pair loop pipelined by hand (HNM_OPT_SCAN_PIPE).
+// HNM_OPT_SCAN_SHAPE), layout 1 with its pair loop pipelined by hand (HNM_OPT_SCAN_PIPE), and that
+// loop with the epilogue on the sparse instruction (HNM_OPT_SCAN_SPARSE) beside it.
 // Diagnostic build only (the scan unit is included as text: the kernel is private to it;
 // cert_shape comes from ncf_cert.o through ncf_cert_internal.h):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -c tools/scan_ablation.hip -o build/scan_ablation.o
@@ -26,7 +27,7 @@ static T* dev_fill(size_t n, float lo, float hi, unsigned seed) {
   return d;
 }
 
-template <int SHAPE, bool PIPE = false>
+template <int SHAPE, bool PIPE = false, bool SPARSE = false>
 static float time_scan(dim3 grid, const ScanArgs& a) {
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0);
@@ -34,7 +35,7 @@ static float time_scan(dim3 grid, const ScanArgs& a) {
   float best = 1e30f;
   for (int rep = 0; rep < 8; ++rep) {
     (void)hipEventRecord(e0);
-    hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, SHAPE, PIPE>), grid, dim3(256), 0, 0, a);
+    hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, SHAPE, PIPE, SPARSE>), grid, dim3(256), 0, 0, a);
     (void)hipEventRecord(e1);
     (void)hipEventSynchronize(e1);
     if (hipGetLastError() != hipSuccess) printf("launch error\n");
@@ -88,6 +89,14 @@ int main() {
                           : shape ? time_scan<1>(grid, a) : time_scan<0>(grid, a);
     printf("ncf16_scan shape %d pipe %d  %7.3f ms  %6.1f TF useful  %5.2f cyc/user-tile/SIMD @2.2GHz\n",
            shape, pipe, ms, useful / (ms * 1e-3) / 1e12, ms * 1e-3 * 2.2e9 / (pairs / 32 / 1024));
+  }
+  // the dense and the sparse epilogue alternating, each figure the best of 7: the pipelined
+  // threshold pass, then the plain loop
+  for (int rep = 0; rep < 12; ++rep) {
+    const int sparse = rep & 1, pipe = rep < 8;
+    const float ms = pipe ? (sparse ? time_scan<1, true, true>(grid, a) : time_scan<1, true>(grid, a))
+                          : (sparse ? time_scan<1, false, true>(grid, a) : time_scan<1>(grid, a));
+    printf("ncf16_scan shape 1 pipe %d sparse %d  %7.3f ms\n", pipe, sparse, ms);
   }
   return 0;
 }
