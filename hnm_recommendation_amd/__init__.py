@@ -1,13 +1,14 @@
 """MI355X-native top-N scoring path of hyunlord/hnm_recommendation.
 
 Embedding lookup -> all-items scoring (NeuralCF / LightGCN / Wide&Deep / MF) -> top-K, and
-the popularity baseline's fit and per-user top-K,
+the popularity baseline's fit and per-user top-K, and item-based collaborative filtering
+(co-occurrence fit, per-user and per-basket top-K),
 as hand-written gfx950 HIP kernels behind the C ABI in include/hnm.h (libhnm_mi355x.so),
 exposed through modules that mirror the reference's `src/models` surface.
 """
 from .evaluation import RecommendationMetrics
-from .models import (LightGCN, MatrixFactorization, NeuralCF, PopularityBaseline, UserHistory,
-                     WideDeep)
+from .models import (ItemCF, LightGCN, MatrixFactorization, NeuralCF, PopularityBaseline,
+                     UserHistory, WideDeep)
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
-           "RecommendationMetrics", "UserHistory"]
+           "ItemCF", "RecommendationMetrics", "UserHistory"]

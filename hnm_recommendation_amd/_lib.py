@@ -161,6 +161,17 @@ _SIGS = {
     # ctx, order, order_val, R, rank, num_items, mask_ptr, mask_idx, B, k, chunk, out_val, out_idx
     "hnm_popularity_topk_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, _p, _p, _i64, C.c_int, C.c_int,
                                        _p, _p]),
+    # ctx, hist_ptr, hist_idx, num_users, num_items, N, shrink, max_history, window, nbr_idx,
+    # nbr_val, item_count
+    "hnm_itemcf_fit_f32": (_i32, [_p, _p, _p, _i64, _i64, C.c_int, C.c_double, _i64, C.c_int, _p,
+                                  _p, _p]),
+    # ctx, nbr_idx, nbr_val, num_items, N, hist_ptr, hist_idx, num_users, user_ids, B, out, ld
+    "hnm_itemcf_scores_f32": (_i32, [_p, _p, _p, _i64, C.c_int, _p, _p, _i64, _p, _i64, _p, _i64]),
+    # ctx, nbr_idx, nbr_val, num_items, N, hist_ptr, hist_idx, num_users, user_ids, B, mask_ptr,
+    # mask_idx, k, out_val, out_idx
+    "hnm_itemcf_topk_f32": (_i32, [_p, _p, _p, _i64, C.c_int, _p, _p, _i64, _p, _i64, _p, _p,
+                                   C.c_int, _p, _p]),
+    "hnm_itemcf_route": (_i32, [_p, C.c_int, _i64, C.POINTER(C.c_int)]),
 }
 
 _lib = None

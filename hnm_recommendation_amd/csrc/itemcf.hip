@@ -1,0 +1,530 @@
+// ItemCF: item-based collaborative filtering over the de-duplicated user -> item CSR
+// (UserHistory.hist_ptr / hist_idx: rows ascending and unique).  No reference counterpart: the
+// contract is stated in include/hnm.h and restated in numpy by tests/test_gpu_itemcf.py.
+//
+// Fit.  Users with more than max_history items are dropped.  Over the kept users
+//   n[i]     = users holding i                         (int32 atomics -> item_count int64)
+//   C[i, j]  = users holding i and j, i != j           (int32 LDS atomics)
+//   sim[i,j] = float( double(C) / ( sqrt(double(n_i) * double(n_j)) + shrink ) )   for C > 0
+// one rounding per operation, contraction off; row i keeps the N best in (sim desc, j asc) order,
+// padded with (-1, 0.0f).  Counts are integers, so the result is the same bits on every run.
+// Shape: histogram -> scan -> fill give the item -> user transpose; then one workgroup per item
+// walks the catalogue in windows of `window` columns of LDS counters: a thread per user of the
+// item finds the window's lower bound in that user's sorted row by binary search and adds 1 per
+// item inside the window; each wave then turns its share of the non-zero counters into sim and
+// offers them to its wave-resident top-N list (clearing the counters as it reads); the four
+// lists are merged at the end.  (sim desc, j asc) is a total order, so the merge order is free.
+//
+// Scores.  score[i] = the fp32 sum of val(j -> i) over the history items j in ascending order,
+// plain adds: one step per j, the up-to-64 neighbours of one j are distinct items (one lane
+// each, no atomics), a workgroup barrier between steps (a lane reads what another wrote).
+//
+// Top-K.  One wave per row with an LDS open-addressing table keyed by item id, sized from
+// h * N (h = history length); slots are claimed by compare-and-swap (two new items of one step
+// may hash alike), the adds are plain.  Then the unmasked entries with score > 0 go through
+// the wave list.  Rows with h * N > ICF_TABLE queue themselves for the dense route: a pool of
+// workspace rows, the same steps, the same selection -- the same bits.
+#include "hnm_device.h"
+#include "hnm_internal.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int ICF_MAX_N = 64;
+// int32 counters per LDS pass.  Measured at the H&M shape (tools/itemcf_bench.py): 4,096 -> 307 ms,
+// 8,192 -> 190 ms, 16,384 (64 KiB, two workgroups a CU) -> 139 ms: fewer passes beat occupancy.
+constexpr int ICF_WINDOW_DEFAULT = 16384;
+constexpr int ICF_WINDOW_MAX = 16384;
+constexpr int ICF_TABLE = 4096;           // LDS table slots of the fused top-K (32 KiB)
+constexpr int ICF_DENSE_POOL = 128;       // workspace rows (and workgroups) of the dense route
+constexpr int ICF_GRID_USERS = 4096;
+
+// ------------------------------------------------------------------ shared device pieces
+// Offer one candidate per lane to a single-register wave list (slot s in lane s, K <= 64).
+__device__ __forceinline__ void icf_offer(float& lv, int& li, float sv, int si, bool valid, int K) {
+  const float tv = hnm_readlane_f(lv, K - 1);
+  const int ti = hnm_readlane_i(li, K - 1);
+  uint64_t m = __ballot(valid && hnm_better(sv, si, tv, ti));
+  while (m) {
+    const int l = __builtin_ctzll(m);
+    m &= m - 1;
+    list1_insert(lv, li, hnm_readlane_f(sv, l), hnm_readlane_i(si, l), K);
+  }
+}
+
+// Fold the lists of waves 1..3 of a 256-thread workgroup into wave 0's (mv / mi: 256 slots of
+// LDS).  Every thread calls it; the result is valid in wave 0.
+__device__ __forceinline__ void icf_merge4(float& lv, int& li, float* mv, int* mi, int K) {
+  const int t = threadIdx.x;
+  mv[t] = lv;
+  mi[t] = li;
+  __syncthreads();
+  if (t < 64) {
+    for (int w = 1; w < 4; ++w) {
+      const float cv = mv[w * 64 + t];
+      const int ci = mi[w * 64 + t];
+      icf_offer(lv, li, cv, ci, ci != HNM_SENTINEL_IDX, K);
+    }
+  }
+}
+
+__device__ __forceinline__ bool icf_masked(const int32_t* midx, int64_t m0, int64_t m1, int item) {
+  const int64_t p = mask_lower_bound(midx, m0, m1, item);
+  return p < m1 && midx[p] == item;
+}
+
+// The history row of batch row b: (first entry, length); a user id out of range raises the
+// error word and gives an empty row.
+__device__ __forceinline__ void icf_row(const int64_t* hist_ptr, int64_t num_users,
+                                        const int64_t* user_ids, int64_t b, unsigned* err,
+                                        int64_t& p0, int64_t& h) {
+  const int64_t u = user_ids ? user_ids[b] : b;
+  p0 = 0;
+  h = 0;
+  if (u < 0 || u >= num_users) {
+    if (threadIdx.x == 0) hnm_flag(err, HNM_ERR_OOB);
+    return;
+  }
+  p0 = hist_ptr[u];
+  h = hist_ptr[u + 1] - p0;
+  if (h < 0) h = 0;
+}
+
+// The (idx, val) lane t < N holds for step s of a history row (idx -1: nothing to add).
+__device__ __forceinline__ void icf_step_load(const int32_t* __restrict__ nbr_idx,
+                                              const float* __restrict__ nbr_val, int64_t I, int N,
+                                              const int32_t* __restrict__ hist_idx, int64_t p0,
+                                              int64_t h, int64_t s, unsigned* err, int& idx,
+                                              float& val) {
+  idx = -1;
+  val = 0.f;
+  const int t = threadIdx.x;
+  if (t < N && s < h) {
+    const int32_t j = hist_idx[p0 + s];
+    if (j < 0 || j >= I) {
+      hnm_flag(err, HNM_ERR_OOB);
+    } else {
+      idx = nbr_idx[(int64_t)j * N + t];
+      val = nbr_val[(int64_t)j * N + t];
+      if (idx >= I) idx = -1;  // a table that was not produced by the fit: never write outside
+    }
+  }
+}
+
+// row[0, I) (zeroed, visible to the workgroup) += the history row, one step per history item in
+// ascending order.  Every thread of the workgroup calls it (h is uniform); step s + 1 is loaded
+// before step s's barrier.
+__device__ __forceinline__ void icf_accumulate_dense(float* row, const int32_t* nbr_idx,
+                                                     const float* nbr_val, int64_t I, int N,
+                                                     const int32_t* hist_idx, int64_t p0,
+                                                     int64_t h, unsigned* err) {
+  int nidx;
+  float nval;
+  icf_step_load(nbr_idx, nbr_val, I, N, hist_idx, p0, h, 0, err, nidx, nval);
+  for (int64_t s = 0; s < h; ++s) {
+    const int cidx = nidx;
+    const float cval = nval;
+    icf_step_load(nbr_idx, nbr_val, I, N, hist_idx, p0, h, s + 1, err, nidx, nval);
+    if (cidx >= 0) row[cidx] = row[cidx] + cval;
+    __syncthreads();  // the next step reads what this one wrote (another lane's item)
+  }
+}
+
+// ------------------------------------------------------------------ fit
+// A user's row if the fit keeps the user (len <= max_history, bounds sane).
+__device__ __forceinline__ bool icf_kept(const int64_t* hist_ptr, int64_t u, int64_t nnz,
+                                         int64_t max_history, unsigned* err, int64_t& p0,
+                                         int64_t& p1) {
+  p0 = hist_ptr[u];
+  p1 = hist_ptr[u + 1];
+  if (p0 < 0 || p1 < p0 || p1 > nnz) {
+    hnm_flag(err, HNM_ERR_OOB);
+    return false;
+  }
+  return max_history <= 0 || p1 - p0 <= max_history;
+}
+
+// FILL = false: cnt[j] += 1 per (kept user, item j).  FILL = true: tusers[cursor[j]++] = u.
+template <bool FILL>
+__global__ __launch_bounds__(256) void icf_transpose_kernel(
+    const int64_t* __restrict__ hist_ptr, const int32_t* __restrict__ hist_idx, int64_t num_users,
+    int64_t I, int64_t nnz, int64_t max_history, int* __restrict__ cnt, int* __restrict__ tusers,
+    unsigned* err) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < num_users; u += stride) {
+    int64_t p0, p1;
+    if (!icf_kept(hist_ptr, u, nnz, max_history, FILL ? nullptr : err, p0, p1)) continue;
+    for (int64_t p = p0; p < p1; ++p) {
+      const int32_t j = hist_idx[p];
+      if (j < 0 || j >= I) {
+        if (!FILL) hnm_flag(err, HNM_ERR_OOB);
+        continue;
+      }
+      const int at = atomicAdd(&cnt[j], 1);
+      if (FILL) tusers[at] = (int)u;
+    }
+  }
+}
+
+// One workgroup: tptr = exclusive scan of cnt (tptr[I] = total), cursor = tptr[0, I),
+// item_count = cnt as int64.
+__global__ __launch_bounds__(1024) void icf_scan_kernel(const int* __restrict__ cnt, int64_t I,
+                                                        int* __restrict__ tptr,
+                                                        int* __restrict__ cursor,
+                                                        int64_t* __restrict__ item_count) {
+  __shared__ int part[1024];
+  const int t = threadIdx.x;
+  const int64_t per = hnm_cdiv(I, 1024);
+  const int64_t b = std::min<int64_t>(I, t * per), e = std::min<int64_t>(I, b + per);
+  int s = 0;
+  for (int64_t x = b; x < e; ++x) s += cnt[x];
+  part[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const int v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int base = part[t] - s;
+  for (int64_t x = b; x < e; ++x) {
+    const int c = cnt[x];
+    tptr[x] = base;
+    cursor[x] = base;
+    item_count[x] = c;
+    base += c;
+  }
+  if (t == 1023) tptr[I] = part[1023];
+}
+
+__device__ __forceinline__ float icf_sim(int c, int ni, int nj, double shrink) {
+#pragma clang fp contract(off)
+  const double prod = (double)ni * (double)nj;
+  const double den = sqrt(prod) + shrink;
+  return (float)((double)c / den);
+}
+
+// One workgroup per item i; W counters of dynamic LDS (at least 512 words: the merge reuses it).
+__global__ __launch_bounds__(256) void icf_cooc_kernel(
+    const int64_t* __restrict__ hist_ptr, const int32_t* __restrict__ hist_idx,
+    const int* __restrict__ cnt, const int* __restrict__ tptr, const int* __restrict__ tusers,
+    int64_t I, int N, double shrink, int W, int32_t* __restrict__ nbr_idx,
+    float* __restrict__ nbr_val) {
+  extern __shared__ int icf_lds[];
+  int* c = icf_lds;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int i = blockIdx.x;
+  const int ni = cnt[i];
+  const int t0 = tptr[i];
+  float lv = -__builtin_inff();
+  int li = HNM_SENTINEL_IDX;
+  if (ni > 0) {  // uniform over the workgroup
+    for (int x = t; x < W; x += 256) c[x] = 0;
+    __syncthreads();
+    for (int64_t w0 = 0; w0 < I; w0 += W) {
+      const int64_t w1 = std::min<int64_t>(I, w0 + W);
+      const int len = (int)(w1 - w0);
+      for (int q = t; q < ni; q += 256) {
+        const int u = tusers[t0 + q];
+        const int64_t p1 = hist_ptr[u + 1];
+        int64_t p = mask_lower_bound(hist_idx, hist_ptr[u], p1, (int)w0);
+        for (; p < p1; ++p) {
+          const int64_t j = hist_idx[p];
+          if (j >= w1) break;
+          if (j >= w0) atomicAdd(&c[j - w0], 1);  // result unused: a non-returning ds_add
+        }
+      }
+      __syncthreads();
+      for (int g = wave * 64; g < len; g += 256) {  // trip count uniform over the wave
+        const int x = g + lane;
+        int cc = 0;
+        if (x < len) {
+          cc = c[x];
+          if (cc) c[x] = 0;
+        }
+        const int j = (int)w0 + x;
+        const bool valid = cc > 0 && j != i;
+        const float sim = valid ? icf_sim(cc, ni, cnt[j], shrink) : 0.f;
+        icf_offer(lv, li, sim, j, valid, N);
+      }
+      __syncthreads();
+    }
+  }
+  icf_merge4(lv, li, reinterpret_cast<float*>(c), c + 256, N);
+  if (t < N) {
+    const bool pad = li == HNM_SENTINEL_IDX;
+    nbr_idx[(int64_t)i * N + t] = pad ? -1 : li;
+    nbr_val[(int64_t)i * N + t] = pad ? 0.f : lv;
+  }
+}
+
+// ------------------------------------------------------------------ scores, top-K
+// One 256-thread workgroup per batch row: out[b, 0 .. I) = the row's scores.
+__global__ __launch_bounds__(256) void icf_scores_kernel(
+    const int32_t* __restrict__ nbr_idx, const float* __restrict__ nbr_val, int64_t I, int N,
+    const int64_t* __restrict__ hist_ptr, const int32_t* __restrict__ hist_idx, int64_t num_users,
+    const int64_t* __restrict__ user_ids, float* out, int64_t ld, unsigned* err) {
+  const int64_t b = blockIdx.x;
+  int64_t p0, h;
+  icf_row(hist_ptr, num_users, user_ids, b, err, p0, h);
+  float* row = out + b * ld;
+  for (int64_t x = threadIdx.x; x < I; x += 256) row[x] = 0.f;
+  __syncthreads();
+  icf_accumulate_dense(row, nbr_idx, nbr_val, I, N, hist_idx, p0, h, err);
+}
+
+__device__ __forceinline__ void icf_store_topk(float lv, int li, int k, float* ov, int64_t* oi) {
+  const int lane = threadIdx.x;
+  if (lane < k) {
+    const bool pad = li == HNM_SENTINEL_IDX;
+    ov[lane] = pad ? -__builtin_inff() : lv;
+    oi[lane] = pad ? -1 : li;
+  }
+}
+
+// One wave per batch row.  Rows whose h * N exceeds the table append themselves to dense_rows.
+__global__ __launch_bounds__(64) void icf_topk_kernel(
+    const int32_t* __restrict__ nbr_idx, const float* __restrict__ nbr_val, int64_t I, int N,
+    const int64_t* __restrict__ hist_ptr, const int32_t* __restrict__ hist_idx, int64_t num_users,
+    const int64_t* __restrict__ user_ids, const int64_t* __restrict__ mptr,
+    const int32_t* __restrict__ midx, int k, float* __restrict__ out_val,
+    int64_t* __restrict__ out_idx, int* __restrict__ dense_rows, int* ndense, unsigned* err) {
+  __shared__ int key[ICF_TABLE];
+  __shared__ float val[ICF_TABLE];
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x;
+  int64_t p0, h;
+  icf_row(hist_ptr, num_users, user_ids, b, err, p0, h);
+  if (h * N > ICF_TABLE) {  // uniform
+    if (lane == 0) dense_rows[atomicAdd(ndense, 1)] = (int)b;
+    return;
+  }
+  int bits = 6;
+  while ((1 << bits) < 2 * h * N && (1 << bits) < ICF_TABLE) ++bits;
+  const int cap = 1 << bits;  // >= h * N: every distinct item finds a slot
+  for (int x = lane; x < cap; x += 64) {
+    key[x] = -1;
+    val[x] = 0.f;
+  }
+  __syncthreads();
+  int nidx;
+  float nval;
+  icf_step_load(nbr_idx, nbr_val, I, N, hist_idx, p0, h, 0, err, nidx, nval);
+  for (int64_t s = 0; s < h; ++s) {
+    const int cidx = nidx;
+    const float cval = nval;
+    icf_step_load(nbr_idx, nbr_val, I, N, hist_idx, p0, h, s + 1, err, nidx, nval);
+    if (cidx >= 0) {
+      unsigned slot = ((unsigned)cidx * 2654435761u) >> (32 - bits);
+      for (;;) {
+        const int prev = atomicCAS(&key[slot], -1, cidx);
+        if (prev == -1 || prev == cidx) break;
+        slot = (slot + 1) & (cap - 1);
+      }
+      val[slot] = val[slot] + cval;  // this step's items are distinct: the slot is this lane's
+    }
+    __syncthreads();  // the next step reads what this one wrote (another lane's item)
+  }
+  int64_t m0 = 0, m1 = 0;
+  if (mptr) {
+    m0 = mptr[b];
+    m1 = mptr[b + 1];
+  }
+  float lv = -__builtin_inff();
+  int li = HNM_SENTINEL_IDX;
+  for (int g = 0; g < cap; g += 64) {
+    const int kx = key[g + lane];
+    const float vx = val[g + lane];
+    bool ok = kx >= 0 && vx > 0.f &&
+              hnm_better(vx, kx, hnm_readlane_f(lv, k - 1), hnm_readlane_i(li, k - 1));
+    if (ok && m1 > m0) ok = !icf_masked(midx, m0, m1, kx);
+    icf_offer(lv, li, vx, kx, ok, k);
+  }
+  icf_store_topk(lv, li, k, out_val + b * k, out_idx + b * k);
+}
+
+// The dense route: workgroup w owns workspace row w and takes the queued rows w, w + grid, ...
+__global__ __launch_bounds__(256) void icf_topk_dense_kernel(
+    const int32_t* __restrict__ nbr_idx, const float* __restrict__ nbr_val, int64_t I, int N,
+    const int64_t* __restrict__ hist_ptr, const int32_t* __restrict__ hist_idx, int64_t num_users,
+    const int64_t* __restrict__ user_ids, const int64_t* __restrict__ mptr,
+    const int32_t* __restrict__ midx, int k, float* __restrict__ out_val,
+    int64_t* __restrict__ out_idx, const int* __restrict__ dense_rows, const int* ndense,
+    float* pool, unsigned* err) {
+  __shared__ float mv[256];
+  __shared__ int mi[256];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int n = *ndense;
+  float* row = pool + (int64_t)blockIdx.x * I;
+  for (int r = blockIdx.x; r < n; r += gridDim.x) {
+    const int64_t b = dense_rows[r];
+    int64_t p0, h;
+    icf_row(hist_ptr, num_users, user_ids, b, err, p0, h);
+    for (int64_t x = t; x < I; x += 256) row[x] = 0.f;
+    __syncthreads();
+    icf_accumulate_dense(row, nbr_idx, nbr_val, I, N, hist_idx, p0, h, err);
+    int64_t m0 = 0, m1 = 0;
+    if (mptr) {
+      m0 = mptr[b];
+      m1 = mptr[b + 1];
+    }
+    float lv = -__builtin_inff();
+    int li = HNM_SENTINEL_IDX;
+    for (int64_t g = wave * 64; g < I; g += 256) {  // trip count uniform over the wave
+      const int64_t x = g + lane;
+      const float vx = x < I ? row[x] : 0.f;
+      bool ok = vx > 0.f && hnm_better(vx, (int)x, hnm_readlane_f(lv, k - 1),
+                                       hnm_readlane_i(li, k - 1));
+      if (ok && m1 > m0) ok = !icf_masked(midx, m0, m1, (int)x);
+      icf_offer(lv, li, vx, (int)x, ok, k);
+    }
+    icf_merge4(lv, li, mv, mi, k);
+    if (t < 64) icf_store_topk(lv, li, k, out_val + b * k, out_idx + b * k);
+    __syncthreads();  // mv / mi and the workspace row are reused by the next queued row
+  }
+}
+
+hnm_status icf_table_check(const char* what, hnm_ctx* ctx, const int32_t* nbr_idx,
+                           const float* nbr_val, int64_t num_items, int N, const int64_t* hist_ptr,
+                           const int32_t* hist_idx, int64_t num_users, int64_t B) {
+  HNM_REQUIRE(ctx, HNM_EINVAL, "%s: ctx is NULL", what);
+  HNM_REQUIRE(N >= 1 && N <= ICF_MAX_N, HNM_EINVAL, "%s: 1 <= N <= %d", what, ICF_MAX_N);
+  HNM_REQUIRE(B >= 0 && num_items >= 0 && num_users >= 0, HNM_EINVAL, "%s: bad size", what);
+  HNM_REQUIRE(B <= INT32_MAX && num_items < INT_BIG, HNM_EUNSUPPORTED,
+              "%s: B or num_items exceeds 2^31 - 1", what);
+  if (B == 0) return HNM_OK;
+  HNM_REQUIRE((nbr_idx && nbr_val) || num_items == 0, HNM_EINVAL, "%s: NULL neighbour table", what);
+  HNM_REQUIRE((hist_ptr && hist_idx) || num_users == 0, HNM_EINVAL, "%s: NULL history", what);
+  return HNM_OK;
+}
+
+}  // namespace
+
+extern "C" hnm_status hnm_itemcf_fit_f32(hnm_ctx* ctx, const int64_t* hist_ptr,
+                                         const int32_t* hist_idx, int64_t num_users,
+                                         int64_t num_items, int N, double shrink,
+                                         int64_t max_history, int window, int32_t* nbr_idx,
+                                         float* nbr_val, int64_t* item_count) {
+  HNM_CTX_DEVICE(ctx);
+  HNM_REQUIRE(ctx, HNM_EINVAL, "itemcf_fit: ctx is NULL");
+  HNM_REQUIRE(N >= 1 && N <= ICF_MAX_N, HNM_EINVAL, "itemcf_fit: 1 <= N <= %d", ICF_MAX_N);
+  HNM_REQUIRE(num_users >= 0 && num_items >= 0 && max_history >= 0, HNM_EINVAL,
+              "itemcf_fit: bad size");
+  HNM_REQUIRE(shrink >= 0.0 && std::isfinite(shrink), HNM_EINVAL,
+              "itemcf_fit: shrink must be finite and >= 0");
+  HNM_REQUIRE(window == 0 || (window >= 64 && window <= ICF_WINDOW_MAX && window % 64 == 0),
+              HNM_EINVAL, "itemcf_fit: window must be 0 or a multiple of 64 in [64, %d]",
+              ICF_WINDOW_MAX);
+  HNM_REQUIRE(num_users <= INT32_MAX && num_items < INT_BIG, HNM_EUNSUPPORTED,
+              "itemcf_fit: num_users or num_items exceeds 2^31 - 1");
+  if (num_items == 0) return HNM_OK;
+  HNM_REQUIRE(nbr_idx && nbr_val && item_count, HNM_EINVAL, "itemcf_fit: NULL output");
+  HNM_REQUIRE((hist_ptr && hist_idx) || num_users == 0, HNM_EINVAL, "itemcf_fit: NULL history");
+  const int64_t I = num_items;
+  int64_t nnz = 0;
+  if (num_users > 0) {  // the transpose is sized by the CSR's last offset
+    HNM_HIP_CHECK(hipMemcpyAsync(&nnz, hist_ptr + num_users, sizeof(int64_t),
+                                 hipMemcpyDeviceToHost, ctx->stream));
+    HNM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  }
+  HNM_REQUIRE(nnz >= 0 && nnz <= INT32_MAX, HNM_EUNSUPPORTED,
+              "itemcf_fit: the history holds %lld entries (0 .. 2^31 - 1 supported)",
+              (long long)nnz);
+  const size_t s_cnt = hnm_align((size_t)I * 4), s_ptr = hnm_align((size_t)(I + 1) * 4),
+               s_usr = hnm_align((size_t)std::max<int64_t>(nnz, 1) * 4);
+  char* ws = nullptr;
+  hnm_status st = hnm_workspace(ctx, 2 * s_cnt + s_ptr + s_usr, (void**)&ws);
+  if (st != HNM_OK) return st;
+  int* cnt = (int*)ws;
+  int* cursor = (int*)(ws + s_cnt);
+  int* tptr = (int*)(ws + 2 * s_cnt);
+  int* tusers = (int*)(ws + 2 * s_cnt + s_ptr);
+  HNM_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)I * 4, ctx->stream));
+  const unsigned ugrid = (unsigned)std::min<int64_t>(ICF_GRID_USERS, hnm_cdiv(num_users, 256));
+  if (num_users > 0) {
+    hipLaunchKernelGGL(icf_transpose_kernel<false>, dim3(ugrid), dim3(256), 0, ctx->stream,
+                       hist_ptr, hist_idx, num_users, I, nnz, max_history, cnt, (int*)nullptr,
+                       ctx->err_dev);
+    HNM_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(icf_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cnt, I, tptr, cursor,
+                     item_count);
+  HNM_LAUNCH_CHECK();
+  if (num_users > 0) {
+    hipLaunchKernelGGL(icf_transpose_kernel<true>, dim3(ugrid), dim3(256), 0, ctx->stream,
+                       hist_ptr, hist_idx, num_users, I, nnz, max_history, cursor, tusers,
+                       ctx->err_dev);
+    HNM_LAUNCH_CHECK();
+  }
+  int W = window ? window : ICF_WINDOW_DEFAULT;
+  W = (int)std::min<int64_t>(W, hnm_cdiv(I, 64) * 64);
+  const size_t lds = (size_t)std::max(W, 512) * 4;
+  hipLaunchKernelGGL(icf_cooc_kernel, dim3((unsigned)I), dim3(256), lds, ctx->stream, hist_ptr,
+                     hist_idx, cnt, tptr, tusers, I, N, shrink, W, nbr_idx, nbr_val);
+  HNM_LAUNCH_CHECK();
+  return HNM_OK;
+}
+
+extern "C" hnm_status hnm_itemcf_scores_f32(hnm_ctx* ctx, const int32_t* nbr_idx,
+                                            const float* nbr_val, int64_t num_items, int N,
+                                            const int64_t* hist_ptr, const int32_t* hist_idx,
+                                            int64_t num_users, const int64_t* user_ids, int64_t B,
+                                            float* out, int64_t ld) {
+  HNM_CTX_DEVICE(ctx);
+  hnm_status st = icf_table_check("itemcf_scores", ctx, nbr_idx, nbr_val, num_items, N, hist_ptr,
+                                  hist_idx, num_users, B);
+  if (st != HNM_OK) return st;
+  if (B == 0 || num_items == 0) return HNM_OK;
+  HNM_REQUIRE(out && ld >= num_items, HNM_EINVAL, "itemcf_scores: NULL output or ld < num_items");
+  hipLaunchKernelGGL(icf_scores_kernel, dim3((unsigned)B), dim3(256), 0, ctx->stream, nbr_idx,
+                     nbr_val, num_items, N, hist_ptr, hist_idx, num_users, user_ids, out, ld,
+                     ctx->err_dev);
+  HNM_LAUNCH_CHECK();
+  return HNM_OK;
+}
+
+extern "C" hnm_status hnm_itemcf_topk_f32(hnm_ctx* ctx, const int32_t* nbr_idx,
+                                          const float* nbr_val, int64_t num_items, int N,
+                                          const int64_t* hist_ptr, const int32_t* hist_idx,
+                                          int64_t num_users, const int64_t* user_ids, int64_t B,
+                                          const int64_t* mask_ptr, const int32_t* mask_idx, int k,
+                                          float* out_val, int64_t* out_idx) {
+  HNM_CTX_DEVICE(ctx);
+  hnm_status st = icf_table_check("itemcf_topk", ctx, nbr_idx, nbr_val, num_items, N, hist_ptr,
+                                  hist_idx, num_users, B);
+  if (st != HNM_OK) return st;
+  HNM_REQUIRE(k >= 0 && k <= 64, HNM_EINVAL, "itemcf_topk: 0 <= k <= 64");
+  if (B == 0 || k == 0) return HNM_OK;
+  HNM_REQUIRE(out_val && out_idx, HNM_EINVAL, "itemcf_topk: NULL output");
+  HNM_REQUIRE(!mask_ptr || mask_idx, HNM_EINVAL, "itemcf_topk: mask_ptr without mask_idx");
+  const int pool_rows = (int)std::min<int64_t>(B, ICF_DENSE_POOL);
+  const size_t s_rows = hnm_align((size_t)B * 4), s_n = 256;
+  char* ws = nullptr;
+  st = hnm_workspace(ctx, s_n + s_rows + (size_t)pool_rows * (size_t)num_items * 4, (void**)&ws);
+  if (st != HNM_OK) return st;
+  int* ndense = (int*)ws;
+  int* dense_rows = (int*)(ws + s_n);
+  float* pool = (float*)(ws + s_n + s_rows);
+  HNM_HIP_CHECK(hipMemsetAsync(ndense, 0, sizeof(int), ctx->stream));
+  hnm_timer_begin(ctx, HNM_TIME_SCORE);
+  hipLaunchKernelGGL(icf_topk_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, nbr_idx, nbr_val,
+                     num_items, N, hist_ptr, hist_idx, num_users, user_ids, mask_ptr, mask_idx, k,
+                     out_val, out_idx, dense_rows, ndense, ctx->err_dev);
+  hnm_timer_end(ctx, HNM_TIME_SCORE);
+  HNM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(icf_topk_dense_kernel, dim3((unsigned)pool_rows), dim3(256), 0, ctx->stream,
+                     nbr_idx, nbr_val, num_items, N, hist_ptr, hist_idx, num_users, user_ids,
+                     mask_ptr, mask_idx, k, out_val, out_idx, dense_rows, ndense, pool,
+                     ctx->err_dev);
+  HNM_LAUNCH_CHECK();
+  return HNM_OK;
+}
+
+extern "C" hnm_status hnm_itemcf_route(hnm_ctx* ctx, int N, int64_t history_len, int* route) {
+  HNM_REQUIRE(ctx && route, HNM_EINVAL, "itemcf_route: NULL argument");
+  HNM_REQUIRE(N >= 1 && N <= ICF_MAX_N && history_len >= 0, HNM_EINVAL,
+              "itemcf_route: 1 <= N <= %d, history_len >= 0", ICF_MAX_N);
+  *route = history_len * N > ICF_TABLE ? 1 : 0;
+  return HNM_OK;
+}

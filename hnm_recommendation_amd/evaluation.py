@@ -20,6 +20,7 @@ only four sums crossing PCIe.  There is no CPU path: inputs go to the GPU (or ra
 """
 from __future__ import annotations
 
+import itertools
 from typing import Dict, Iterable, Optional
 
 import numpy as np
@@ -290,7 +291,8 @@ def evaluate_model(model, user_ids: torch.Tensor, truth_ptr: torch.Tensor,
     `evaluate_recommendations` over all users (the `benchmark_models.py:151-167` loop:
     predict, top-12, metrics)."""
     dev = model.device
-    _lib.require_gpu(next(model.parameters()))
+    # a fitted model (PopularityBaseline, ItemCF) has buffers and no parameter
+    _lib.require_gpu(next(itertools.chain(model.parameters(), model.buffers())))
     u = torch.as_tensor(user_ids).to(device=dev, dtype=torch.int64)
     tp = truth_ptr.to(device=dev, dtype=torch.int64)
     ti = truth_idx.to(device=dev, dtype=torch.int64)

@@ -4,7 +4,8 @@ from .matrix_factorization import MatrixFactorization
 from .neural_cf import NeuralCF
 from .popularity import PopularityBaseline
 from .base import UserHistory
+from .item_cf import ItemCF
 from .wide_deep import WideDeep
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
-           "UserHistory"]
+           "ItemCF", "UserHistory"]

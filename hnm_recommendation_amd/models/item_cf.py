@@ -1,0 +1,277 @@
+"""ItemCF: item-based collaborative filtering (no reference module: `GEMINI.md` stage 3 names it
+among the baselines, and the reference's data analysis names "item similarity" as the answer to
+its cold-start customers, but `src/models` never built it).
+
+Three HIP entries (`csrc/itemcf.hip`, contract in `include/hnm.h`):
+
+* `hnm_itemcf_fit_f32` -- the fit: co-occurrence counts over the device-resident `UserHistory`
+  CSR, cosine similarity with shrinkage in float64 rounded once to float32, the
+  `num_neighbors` best per item in (sim descending, item ascending) order.  Integer atomics
+  only: the same bits on every run.
+* `hnm_itemcf_scores_f32` -- dense rows (`predict_all_items`): score[i] = the fp32 sum of
+  sim(j -> i) over the history items j in ascending order.
+* `hnm_itemcf_topk_f32` -- the answer: one wave per row over an LDS table instead of a
+  [B, num_items] matrix; a row is a user's history or, without user ids, a basket
+  (`recommend_for_items`: a visitor without a user index).
+
+Top-K convention (as `PopularityBaseline`): the unmasked items with score > 0 in (score
+descending, item ascending) order, rows with fewer than k of them end in (-inf, -1).  History
+items are not excluded by themselves: the filter does that, as for every other model.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..evaluation import RecommendationMetrics
+from .base import RecModule, UserHistory, _history_arrays, dense_topk, empty_topk, filter_csr
+
+MAX_NEIGHBORS = 64   # one lane per neighbour
+FUSED_MAX_K = 64     # hnm_itemcf_topk_f32; above: dense rows + dense_topk
+
+
+class ItemCF(RecModule):
+    def __init__(self, num_users: int, num_items: int, num_neighbors: int = 64,
+                 shrink: float = 0.0, max_history: int = 0, top_k: int = 12):
+        super().__init__()
+        self.save_hyperparameters()
+        if not 1 <= int(num_neighbors) <= MAX_NEIGHBORS:
+            raise ValueError(f"num_neighbors must be in [1, {MAX_NEIGHBORS}]")
+        if not float(shrink) >= 0.0 or not np.isfinite(shrink):
+            raise ValueError("shrink must be finite and >= 0")
+        if int(max_history) < 0:
+            raise ValueError("max_history must be >= 0 (0 = no cap)")
+        self.num_users, self.num_items = int(num_users), int(num_items)
+        self.num_neighbors = int(num_neighbors)
+        self.shrink, self.max_history, self.top_k = float(shrink), int(max_history), int(top_k)
+        shape = (self.num_items, self.num_neighbors)
+        self.register_buffer("neighbor_idx", torch.full(shape, -1, dtype=torch.int32))
+        self.register_buffer("neighbor_val", torch.zeros(shape, dtype=torch.float32))
+        self.register_buffer("item_count", torch.zeros(self.num_items, dtype=torch.int64))
+        self.history: Optional[UserHistory] = None
+        self._is_fitted: Optional[bool] = False   # None: unknown (a loaded state), looked up once
+        self.metrics = RecommendationMetrics(top_k=self.top_k)
+
+    @property
+    def device(self) -> torch.device:
+        return self.neighbor_idx.device
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        out = super().load_state_dict(state_dict, *args, **kwargs)
+        self._is_fitted = None
+        return out
+
+    def _fitted(self):
+        if self._is_fitted is None:  # a loaded table is fitted when it counted anything
+            self._is_fitted = bool((self.item_count > 0).any())
+        if not self._is_fitted:
+            raise RuntimeError("not fitted: call fit_interactions / fit_history, or load a "
+                               "fitted state_dict")
+
+    # ------------------------------------------------------------------ fitting
+    def set_history(self, history: Optional[UserHistory]):
+        """The history `recommend*` and `predict_all_items` read a user's row from."""
+        if history is not None:
+            if not isinstance(history, UserHistory):
+                raise TypeError("history must be a UserHistory")
+            if history.num_items != self.num_items or history.num_users != self.num_users:
+                raise ValueError(f"history built for {history.num_users} users x "
+                                 f"{history.num_items} items, model has {self.num_users} x "
+                                 f"{self.num_items}")
+        self.history = history
+        return self
+
+    def fit_history(self, history: UserHistory, *, _window: int = 0):
+        """Fit on a `UserHistory` and keep it as the model's history: one
+        `hnm_itemcf_fit_f32` call (`_window`: item columns per LDS pass, for tests)."""
+        _lib.require_gpu(self.neighbor_idx)
+        self.set_history(history)
+        dev = self.device
+        if history.device != dev:
+            raise ValueError(f"history lives on {history.device}, the model on {dev}")
+        for name, dtype in (("neighbor_idx", torch.int32), ("neighbor_val", torch.float32),
+                            ("item_count", torch.int64)):
+            t = getattr(self, name)
+            if t.dtype != dtype or not t.is_contiguous():
+                setattr(self, name, t.to(dtype).contiguous())
+        _lib.check(_lib.fn("hnm_itemcf_fit_f32")(
+            _lib.ctx(dev), _lib.ptr(history.hist_ptr), _lib.ptr(history.hist_idx), self.num_users,
+            self.num_items, self.num_neighbors, self.shrink, self.max_history, int(_window),
+            _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val), _lib.ptr(self.item_count)),
+            "hnm_itemcf_fit_f32")
+        _lib.sync_check(dev)
+        self._is_fitted = True
+        return self
+
+    def fit_interactions(self, user_ids, item_ids, *, _window: int = 0):
+        """Fit from (user, item) interaction arrays or tensors (duplicates allowed; ids out of
+        range raise IndexError): builds the `UserHistory`, keeps it, runs the fit."""
+        _lib.require_gpu(self.neighbor_idx)
+        u = user_ids.detach().cpu().numpy() if isinstance(user_ids, torch.Tensor) else user_ids
+        i = item_ids.detach().cpu().numpy() if isinstance(item_ids, torch.Tensor) else item_ids
+        hist = UserHistory.from_interactions(np.asarray(u).reshape(-1), np.asarray(i).reshape(-1),
+                                             self.num_users, self.num_items, self.device)
+        return self.fit_history(hist, _window=_window)
+
+    # ------------------------------------------------------------------ answering
+    def _users(self, user_ids):
+        """(int64 contiguous device ids, host_checked) -- RecModule._ids without a parameter."""
+        if not isinstance(user_ids, torch.Tensor):
+            user_ids = torch.as_tensor(user_ids)
+        user_ids = user_ids.reshape(-1)
+        _lib.require_gpu(self.neighbor_idx)
+        host = not user_ids.is_cuda
+        if host and user_ids.numel() > 0:
+            lo, hi = int(user_ids.min()), int(user_ids.max())
+            if lo < 0 or hi >= self.num_users:
+                raise IndexError(f"index out of range in self (user_ids must be in "
+                                 f"[0, {self.num_users}))")
+        return user_ids.to(device=self.device, dtype=torch.int64).contiguous(), host
+
+    def _need_history(self) -> UserHistory:
+        if self.history is None:
+            raise RuntimeError("no history: call set_history (or fit_interactions) first")
+        if self.history.device != self.device:
+            raise ValueError(f"history lives on {self.history.device}, the model on {self.device}")
+        return self.history
+
+    def _dense(self, hptr, hidx, rows: int, u: Optional[torch.Tensor], B: int) -> torch.Tensor:
+        out = torch.empty(B, self.num_items, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.fn("hnm_itemcf_scores_f32")(
+            _lib.ctx(self.device), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
+            self.num_items, self.num_neighbors, _lib.ptr(hptr), _lib.ptr(hidx), rows, _lib.ptr(u),
+            B, _lib.ptr(out), out.stride(0) if B else self.num_items), "hnm_itemcf_scores_f32")
+        return out
+
+    def _topk(self, hptr, hidx, rows: int, u: Optional[torch.Tensor], B: int, mptr, midx, k: int):
+        """(scores [B, k], items [B, k]) of B history rows (u None: the CSR's own rows)."""
+        dev = self.device
+        if k <= FUSED_MAX_K:
+            out_v = torch.empty(B, k, dtype=torch.float32, device=dev)
+            out_i = torch.empty(B, k, dtype=torch.int64, device=dev)
+            _lib.check(_lib.fn("hnm_itemcf_topk_f32")(
+                _lib.ctx(dev), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
+                self.num_items, self.num_neighbors, _lib.ptr(hptr), _lib.ptr(hidx), rows,
+                _lib.ptr(u), B, _lib.ptr(mptr), _lib.ptr(midx), k, _lib.ptr(out_v),
+                _lib.ptr(out_i)), "hnm_itemcf_topk_f32")
+            return out_v, out_i
+        # k > 64: the dense rows and the row top-k kernel; slots without a positive score
+        # (zero scores, masked items) become (-inf, -1)
+        if B == 0:
+            return empty_rows(B, k, dev)
+        out_v, out_i = dense_topk(self._dense(hptr, hidx, rows, u, B), k, mptr, midx)
+        pad = ~(out_v > 0)
+        return out_v.masked_fill(pad, float("-inf")), out_i.masked_fill(pad, -1)
+
+    def predict_all_items(self, user_ids) -> torch.Tensor:
+        """[B, num_items] scores of the users' history rows."""
+        self._fitted()
+        u, host = self._users(user_ids)
+        h = self._need_history()
+        out = self._dense(h.hist_ptr, h.hist_idx, h.num_users, u, u.numel())
+        self._check(self.device, host)
+        return out
+
+    def recommend_with_scores(self, user_ids, filter_items=None, k: Optional[int] = None):
+        """(scores [B, k] f32, items [B, k] int64): per user the items with score > 0 not in
+        `filter_items` (a `{user: items}` dict or a `UserHistory`), best first; short rows end
+        in (-inf, -1).  k is clamped to num_items."""
+        self._fitted()
+        k = self.top_k if k is None else k
+        u, host = self._users(user_ids)
+        h = self._need_history()
+        mptr, midx = filter_csr(u, filter_items, self.num_items, u.device)
+        kk = min(k, self.num_items)
+        if kk <= 0:
+            return empty_topk(k, u)
+        out = self._topk(h.hist_ptr, h.hist_idx, h.num_users, u, u.numel(), mptr, midx, kk)
+        self._check(self.device, host)
+        return out
+
+    def recommend(self, user_ids, filter_items=None) -> torch.Tensor:
+        """[B, top_k] int64 item ids (-1 past the last item with a positive score)."""
+        self._check_top_k()
+        with torch.no_grad():
+            return self.recommend_with_scores(user_ids, filter_items=filter_items,
+                                              k=self.top_k)[1]
+
+    def forward(self, user_ids) -> torch.Tensor:
+        """`recommend` filtered by the model's own history."""
+        return self.recommend(user_ids, filter_items=self.history)
+
+    def _validation_topk(self, batch):
+        # held-out purchases are scored against what the model was fitted on
+        return self.forward(batch["user_ids"])
+
+    def _basket_csr(self, baskets):
+        """(ptr int64[n + 1], idx int32, n) on the device from a list of item-id iterables
+        (sorted and de-duplicated here; ids outside [-num_items, num_items) raise IndexError)
+        or a (ptr, idx) CSR whose rows already are ascending and unique."""
+        dev = self.device
+        if isinstance(baskets, tuple) and len(baskets) == 2 and all(
+                isinstance(x, (torch.Tensor, np.ndarray)) for x in baskets):
+            ptr = torch.as_tensor(baskets[0]).reshape(-1).to(torch.int64)
+            idx = torch.as_tensor(baskets[1]).reshape(-1).to(torch.int32)
+            if ptr.numel() < 1:
+                raise ValueError("a basket CSR needs ptr of at least one entry")
+            p = ptr.cpu()
+            if int(p[0]) != 0 or bool((p[1:] < p[:-1]).any()) or int(p[-1]) > idx.numel():
+                raise ValueError("basket ptr must start at 0, not decrease and end within idx")
+        else:
+            sets = [list(b) for b in baskets]
+            p, i = _history_arrays(range(len(sets)), sets, self.num_items)
+            ptr, idx = torch.from_numpy(p), torch.from_numpy(i)
+        if idx.numel() == 0:
+            idx = torch.zeros(1, dtype=torch.int32)
+        return ptr.to(dev).contiguous(), idx.to(dev).contiguous(), ptr.numel() - 1
+
+    def recommend_for_items(self, baskets, filter_seen: bool = True, k: Optional[int] = None):
+        """(scores [n, k], items [n, k]) for n baskets of item ids -- visitors without a user
+        index.  `filter_seen` removes each basket's own items from its answer."""
+        self._fitted()
+        _lib.require_gpu(self.neighbor_idx)
+        k = self.top_k if k is None else k
+        ptr, idx, n = self._basket_csr(baskets)
+        kk = min(k, self.num_items)
+        if kk <= 0:
+            return empty_topk(k, ptr[:n])
+        mptr, midx = (ptr, idx) if filter_seen else (None, None)
+        out = self._topk(ptr, idx, n, None, n, mptr, midx, kk)
+        _lib.sync_check(self.device)   # a CSR given by the caller may hold any id
+        return out
+
+    def similar_items(self, item_ids, k: Optional[int] = None):
+        """(sim [n, k] f32, items [n, k] int64): the k nearest neighbours of each item, rows of
+        the fitted table (short rows end in (0.0, -1))."""
+        self._fitted()
+        k = self.num_neighbors if k is None else int(k)
+        if not 0 <= k <= self.num_neighbors:
+            raise ValueError(f"k must be in [0, num_neighbors = {self.num_neighbors}]")
+        ids = torch.as_tensor(item_ids).reshape(-1).to(device=self.device, dtype=torch.int64)
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.num_items):
+            raise IndexError(f"item ids must be in [0, {self.num_items})")
+        return self.neighbor_val[ids, :k], self.neighbor_idx[ids, :k].to(torch.int64)
+
+    def scoring_route(self, user_ids) -> List[str]:
+        """Per user "fused" (the LDS table) or "dense" (a workspace row): what
+        `hnm_itemcf_topk_f32` does with that history length.  The caller cannot choose."""
+        u, _ = self._users(user_ids)
+        h = self._need_history()
+        lens = (h.hist_ptr[u + 1] - h.hist_ptr[u]).cpu().tolist()
+        c = _lib.ctx(self.device)
+        out = []
+        for n in lens:
+            route = C.c_int(-1)
+            _lib.check(_lib.fn("hnm_itemcf_route")(c, self.num_neighbors, int(n),
+                                                   C.byref(route)), "hnm_itemcf_route")
+            out.append("dense" if route.value == 1 else "fused")
+        return out
+
+
+def empty_rows(B: int, k: int, device):
+    return (torch.empty(B, k, dtype=torch.float32, device=device),
+            torch.empty(B, k, dtype=torch.int64, device=device))

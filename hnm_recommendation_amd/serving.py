@@ -21,6 +21,10 @@ article-metadata tables (out of scope: SURVEY §2):
 * `Recommender.add_popularity_baseline` -- `_load_popularity_baseline` (`serve.py:260-280`):
   the fitted `PopularityBaseline` under "popularity_baseline", the model `"best"` falls back
   to when no checkpoint carries a `test_map` (`:415-430`).
+* `Recommender.add_item_cf` / `get_recommendations_for_items` -- no reference counterpart: the
+  fitted `ItemCF` under "item_cf", and the answer for a visitor without a user index (a basket
+  of item ids).  ItemCF rows that run out of co-bought items are back-filled from the
+  popularity baseline when one is registered.
 """
 from __future__ import annotations
 
@@ -32,7 +36,8 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import torch
 
-from .models import LightGCN, MatrixFactorization, NeuralCF, PopularityBaseline, WideDeep
+from .models import (ItemCF, LightGCN, MatrixFactorization, NeuralCF, PopularityBaseline,
+                     WideDeep)
 from .models.base import UserHistory
 
 logger = logging.getLogger(__name__)
@@ -41,10 +46,11 @@ logger = logging.getLogger(__name__)
 MAX_NUM_ITEMS = 100
 
 BASELINE = "popularity_baseline"  # serve.py:273: the name the reference registers it under
+ITEM_CF = "item_cf"
 
 # serve.py:238-248, tested in this order
 _DISPATCH = (("matrix_factorization", MatrixFactorization), ("neural_cf", NeuralCF),
-             ("wide_deep", WideDeep), ("lightgcn", LightGCN))
+             ("wide_deep", WideDeep), ("lightgcn", LightGCN), (ITEM_CF, ItemCF))
 
 
 def load_checkpoint(path: str, device="cpu") -> Dict:
@@ -131,6 +137,17 @@ class Recommender:
         self.add_model(BASELINE, model)
         return model
 
+    def add_item_cf(self, user_ids, item_ids, **kw) -> ItemCF:
+        """Fit an `ItemCF` (keywords: num_neighbors, shrink, max_history, top_k) on the
+        transactions' (user, item) pairs and register it as "item_cf".  Its history becomes the
+        recommender's device history when the recommender has none."""
+        model = ItemCF(self.num_users, self.num_items, **kw).to(self.device)
+        model.fit_interactions(user_ids, item_ids)
+        self.add_model(ITEM_CF, model)
+        if not self.user_history and self._history_dev is None:
+            self._history_dev = model.history
+        return model
+
     def load_checkpoints(self, checkpoint_dir: str, graph=None) -> List[str]:
         """`_load_models` (`serve.py:170-209`): every `**/*.ckpt`, name = parent dir."""
         loaded = []
@@ -158,9 +175,7 @@ class Recommender:
     def _device_history(self) -> Optional[UserHistory]:
         """The purchase history as a device-resident CSR (built once, on first use): each
         filtered batch gathers its rows on the GPU instead of building a mask on the host."""
-        if not self.user_history:
-            return None
-        if self._history_dev is None:
+        if self._history_dev is None and self.user_history:
             self._history_dev = UserHistory(self.user_history, self.num_users, self.num_items,
                                             self.device)
         return self._history_dev
@@ -213,19 +228,85 @@ class Recommender:
                 "department_name": None, "score": score}
 
     # ------------------------------------------------------------------ requests
-    def _score_batch(self, model, idx: List[int], num_items: int, filter_purchased: bool):
+    def _check_num_items(self, num_items):
         # serve.py:56 RecommendationRequest: num_items = Field(12, ge=1, le=100)
         hi = min(MAX_NUM_ITEMS, self.num_items)
         if isinstance(num_items, bool) or not isinstance(num_items, int) or not 1 <= num_items <= hi:
             raise ValueError(f"num_items must be an integer in [1, {hi}]")
+
+    def _back_fill(self, vals, items, fill):
+        """ItemCF rows that end in -1 (fewer than k co-bought items): continue each with the
+        popularity list `fill(rows)` gives for those rows (same k, same filter), skipping what
+        the row already holds -- k entries always suffice.  Filled entries carry their
+        popularity as the score.  On the host: lists of at most 100 entries."""
+        short = [r for r, row in enumerate(items) if row and row[-1] < 0]
+        if not short or BASELINE not in self.models:
+            return
+        pv, pi = fill(short)
+        for r, fv, fi in zip(short, pv, pi):
+            n = next(j for j, it in enumerate(items[r]) if it < 0)
+            have = set(items[r][:n])
+            for v, it in zip(fv, fi):
+                if n == len(items[r]) or it < 0:
+                    break
+                if it not in have:
+                    vals[r][n], items[r][n] = v, it
+                    n += 1
+
+    @staticmethod
+    def _trim(vals, items):
+        """Drop the (-inf, -1) tail of short rows: a response lists real items only."""
+        for r, row in enumerate(items):
+            n = next((j for j, it in enumerate(row) if it < 0), len(row))
+            vals[r], items[r] = vals[r][:n], row[:n]
+
+    def _score_batch(self, model, idx: List[int], num_items: int, filter_purchased: bool):
+        self._check_num_items(num_items)
         # host ids: range-checked on the host by the model (no device-side check / sync),
         # then one fused scoring + history-mask + top-k call; the history mask is gathered
         # on the GPU from the device-resident history (serve.py:350-352)
         users = torch.tensor(idx, dtype=torch.int64)
         hist = self._device_history() if filter_purchased else None
+        if isinstance(model, ItemCF) and model.history is None:  # built from a checkpoint
+            model.set_history(self._device_history())
         with torch.no_grad():
             vals, items = model.recommend_with_scores(users, filter_items=hist, k=num_items)
-        return vals.cpu().tolist(), items.cpu().tolist()
+        vals, items = vals.cpu().tolist(), items.cpu().tolist()
+        if isinstance(model, ItemCF):
+            def fill(rows):
+                with torch.no_grad():
+                    pv, pi = self.models[BASELINE].recommend_with_scores(
+                        users[rows], filter_items=hist, k=num_items)
+                return pv.cpu().tolist(), pi.cpu().tolist()
+            self._back_fill(vals, items, fill)
+            self._trim(vals, items)
+        return vals, items
+
+    def get_recommendations_for_items(self, item_ids, num_items: int = 12,
+                                      model_name: str = ITEM_CF,
+                                      include_scores: bool = False) -> Dict:
+        """A visitor without a user index: recommendations from a basket of item indices (the
+        basket's own items are not recommended back).  ValueError for an unknown model, a model
+        that cannot answer from items, or an item outside [0, num_items)."""
+        self._check_num_items(num_items)
+        name, model = self._resolve_model(model_name)
+        if not isinstance(model, ItemCF):
+            raise ValueError(f"model {name} cannot answer from a basket of items")
+        basket = sorted({int(i) for i in item_ids})
+        if basket and not 0 <= basket[0] <= basket[-1] < self.num_items:
+            raise ValueError(f"item indices must be in [0, {self.num_items})")
+        with torch.no_grad():
+            vals, items = model.recommend_for_items([basket], filter_seen=True, k=num_items)
+        vals, items = vals.cpu().tolist(), items.cpu().tolist()
+
+        def fill(rows):
+            with torch.no_grad():
+                pv, pi = self.models[BASELINE].recommend_with_scores(
+                    torch.zeros(1, dtype=torch.int64), filter_items={0: set(basket)}, k=num_items)
+            return pv.cpu().tolist(), pi.cpu().tolist()
+        self._back_fill(vals, items, fill)
+        self._trim(vals, items)
+        return self._result(None, name, vals[0], items[0], include_scores)
 
     def _result(self, user_id, model_name, vals, items, include_scores):
         recs = [self._item_info(int(i), float(v) if include_scores else None)

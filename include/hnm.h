@@ -695,6 +695,50 @@ hnm_status hnm_popularity_topk_f32(hnm_ctx* ctx, const int64_t* order, const flo
                                    const int64_t* mask_ptr, const int32_t* mask_idx, int64_t B,
                                    int k, int chunk, float* out_val, int64_t* out_idx);
 
+/* ---- ItemCF: item-based collaborative filtering (no reference counterpart) ---------------
+ * Fit.  hist_ptr int64[num_users + 1] / hist_idx int32: the de-duplicated user -> item CSR
+ * (rows ascending and unique: UserHistory's layout).  A user with more than max_history items
+ * is dropped (0 = no cap).  Over the kept users, n[i] = users holding i, C[i, j] = users
+ * holding both i and j (i != j), and for C[i, j] > 0
+ *   sim[i, j] = (float)( (double)C / ( sqrt((double)n_i * (double)n_j) + shrink ) )
+ * in float64 with one rounding per operation and no fma, rounded once to float32.  Row i of
+ * nbr_idx int32[num_items, N] / nbr_val f32[num_items, N] holds the N largest entries in
+ * (sim descending, j ascending) order, padded with (-1, 0.0f); item_count int64[num_items] =
+ * n.  1 <= N <= 64.  Integer atomics only: the same bits on every run.  `window`: item columns
+ * counted per LDS pass (0 = default 16,384; else a multiple of 64 in [64, 16384]).  The item ->
+ * user transpose lives in the ctx workspace; the call reads the CSR's last offset back (one
+ * stream sync).  Item ids outside [0, num_items) and rows outside the CSR raise the ctx error
+ * word (HNM_EOOB from hnm_ctx_check) and are skipped.  History entries and users: < 2^31. */
+hnm_status hnm_itemcf_fit_f32(hnm_ctx* ctx, const int64_t* hist_ptr, const int32_t* hist_idx,
+                              int64_t num_users, int64_t num_items, int N, double shrink,
+                              int64_t max_history, int window, int32_t* nbr_idx, float* nbr_val,
+                              int64_t* item_count);
+/* Dense scores of B history rows: out[b, i] (row stride ld >= num_items) = the fp32 sum of
+ * nbr_val(j -> i) over the items j of the row in ascending order, plain adds from the first
+ * term; 0.0f where no j points to i.  Row b is the history of user_ids[b], or row b of the CSR
+ * itself when user_ids is NULL (then B <= num_users: a CSR of baskets).  A user id outside
+ * [0, num_users) raises the error word and scores as an empty history. */
+hnm_status hnm_itemcf_scores_f32(hnm_ctx* ctx, const int32_t* nbr_idx, const float* nbr_val,
+                                 int64_t num_items, int N, const int64_t* hist_ptr,
+                                 const int32_t* hist_idx, int64_t num_users,
+                                 const int64_t* user_ids, int64_t B, float* out, int64_t ld);
+/* Fused top-K of the same scores, 0 <= k <= 64: row b of out_val / out_idx [B, k] holds the
+ * items with score > 0 that are not in row b of the CSR mask (mask_ptr int64[B + 1] / mask_idx
+ * int32, rows ascending; both may be NULL), in (score descending, item ascending) order; slots
+ * past the last such item hold (-inf, -1).  History items are not excluded by themselves.  One
+ * wave per row over an LDS table sized from h_b * N (h_b = the row's history length); rows with
+ * h_b * N > 4,096 take the dense route (a workspace row, the same additions in the same order,
+ * the same selection: the same bits) -- hnm_itemcf_route tells which.  B = 0 or k = 0: HNM_OK,
+ * nothing launched. */
+hnm_status hnm_itemcf_topk_f32(hnm_ctx* ctx, const int32_t* nbr_idx, const float* nbr_val,
+                               int64_t num_items, int N, const int64_t* hist_ptr,
+                               const int32_t* hist_idx, int64_t num_users,
+                               const int64_t* user_ids, int64_t B, const int64_t* mask_ptr,
+                               const int32_t* mask_idx, int k, float* out_val, int64_t* out_idx);
+/* *route = 0: a row of history_len items takes the fused LDS route of hnm_itemcf_topk_f32 with
+ * N neighbours per item; 1: the dense route.  No launch, no sync. */
+hnm_status hnm_itemcf_route(hnm_ctx* ctx, int N, int64_t history_len, int* route);
+
 #ifdef __cplusplus
 }
 #endif
