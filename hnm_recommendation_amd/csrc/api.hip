@@ -205,6 +205,26 @@ hnm_status hnm_fill_f32(hnm_ctx* ctx, float* p, int64_t n, float v) {
   return HNM_OK;
 }
 
+// Sorted rows [B, K]: entries below the row's bound become empty slots (-inf, -1).
+__global__ void trim_below_kernel(float* __restrict__ ov, int64_t* __restrict__ oi, int64_t n,
+                                  int K, const float* __restrict__ lb) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= n) return;
+  if (ov[x] < lb[x / K]) {
+    ov[x] = -__builtin_inff();
+    oi[x] = -1;
+  }
+}
+
+hnm_status hnm_topk_trim_below(hnm_ctx* ctx, float* ov, int64_t* oi, int64_t B, int K,
+                               const float* lb) {
+  if (B <= 0 || !ov || !oi || !lb) return HNM_OK;
+  hipLaunchKernelGGL(trim_below_kernel, dim3((unsigned)hnm_cdiv(B * K, 256)), dim3(256), 0,
+                     ctx->stream, ov, oi, B * K, K, lb);
+  HNM_LAUNCH_CHECK();
+  return HNM_OK;
+}
+
 extern "C" hnm_status hnm_ctx_reserve(hnm_ctx* ctx, size_t bytes) {
   HNM_CTX_DEVICE(ctx);
   HNM_REQUIRE(ctx, HNM_EINVAL, "ctx is NULL");

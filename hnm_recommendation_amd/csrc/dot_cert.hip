@@ -1038,7 +1038,10 @@ static hnm_status dot_cert_finish_impl(hnm_ctx* ctx, const DotArgs& a, bool bias
   DotArgs af = a;
   af.rows = x.ovf_rows;
   af.nrows = x.ovf_cnt;
-  return dot_list_pass(ctx, af, bias, x.cv, x.ci, ov, oi);
+  hnm_status st = dot_list_pass(ctx, af, bias, x.cv, x.ci, ov, oi);
+  if (st || !short_ok) return st;
+  // short rows: what the scan appended below the caller's bound depends on f16 rounding
+  return hnm_topk_trim_below(ctx, ov, oi, a.B, a.K, lb);
 }
 
 hnm_status dot_cert_finish(hnm_ctx* ctx, const DotArgs& a, bool bias, void* scratch,

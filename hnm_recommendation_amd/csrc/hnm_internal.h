@@ -212,3 +212,8 @@ hnm_status hnm_topk_merge_i32(hnm_ctx* ctx, const float* cv, const int32_t* ci, 
 
 // p[0, n) = v on the ctx stream
 hnm_status hnm_fill_f32(hnm_ctx* ctx, float* p, int64_t n, float v);
+// Two-phase finish with short_ok: entries of the sorted rows ov / oi [B, K] that score below the
+// caller's bound lb[b] become empty slots (-inf, -1), so a short row is exactly the row's items
+// at or above its bound whatever the scan happened to append below it (no-op when ov is NULL).
+hnm_status hnm_topk_trim_below(hnm_ctx* ctx, float* ov, int64_t* oi, int64_t B, int K,
+                               const float* lb);

@@ -734,7 +734,11 @@ hnm_status ncf_cert_finish(hnm_ctx* ctx, const hnm_ncf_weights* w, const NcfTabs
     return HNM_OK;
   }
   // exact fp32 scan over all items for the queued rows (device-side row list)
-  return ncf_list_rows(ctx, w, t, B, mptr, midx, K, x.ovf_rows, x.ovf_cnt, x.cv, x.ci, ov, oi);
+  hnm_status st =
+      ncf_list_rows(ctx, w, t, B, mptr, midx, K, x.ovf_rows, x.ovf_cnt, x.cv, x.ci, ov, oi);
+  if (st || !short_ok) return st;
+  // short rows: what the scan appended below the caller's bound depends on f16 rounding
+  return hnm_topk_trim_below(ctx, ov, oi, B, K, lb);
 }
 
 hnm_status ncf_cert_topk(hnm_ctx* ctx, const hnm_ncf_weights* w, const NcfTabs& t, int64_t B,

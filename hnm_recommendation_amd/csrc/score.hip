@@ -274,12 +274,18 @@ __global__ __launch_bounds__(256) void thresh_select_kernel(const int* __restric
                                                             float* __restrict__ ov,
                                                             int64_t* __restrict__ oi,
                                                             int32_t* __restrict__ ovf_rows,
-                                                            int32_t* __restrict__ ovf_cnt) {
+                                                            int32_t* __restrict__ ovf_cnt,
+                                                            unsigned long long* __restrict__ stats) {
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   const int lane = threadIdx.x & 63;
   const int n = cnt[b];
-  if (n > cap || n < K) {
+  const bool ovf = n > cap || n < K;
+  if (stats && lane == 0) {  // HNM_OPT_STATS: rows, appended candidates, fallback rows
+    if (b == 0) atomicAdd(&stats[0], (unsigned long long)B);
+    atomicAdd(&stats[ovf ? 2 : 1], ovf ? 1ull : (unsigned long long)n);
+  }
+  if (ovf) {
     if (lane == 0) ovf_rows[atomicAdd(ovf_cnt, 1)] = (int32_t)b;
     return;
   }
@@ -568,7 +574,8 @@ extern "C" hnm_status hnm_dot_topk_f32(hnm_ctx* ctx, const float* user_tab, int6
   HNM_LAUNCH_CHECK();
   // 3. exact top-K of the appended candidates; overflowing rows -> fallback list
   hipLaunchKernelGGL(thresh_select_kernel, dim3((unsigned)hnm_cdiv(B, 4)), dim3(256), 0,
-                     ctx->stream, cnt, bv, bi, cap, B, k, out_val, out_idx, ovf_rows, ovf_cnt);
+                     ctx->stream, cnt, bv, bi, cap, B, k, out_val, out_idx, ovf_rows, ovf_cnt,
+                     ctx->stats_on ? ctx->stats_dev : nullptr);
   HNM_LAUNCH_CHECK();
   // 4. fallback: exact LIST pass restricted (on device) to the queued rows
   DotArgs af = a;

@@ -127,7 +127,9 @@ enum { HNM_OPT_PREFILTER = 1,
 hnm_status hnm_ctx_set_option(hnm_ctx* ctx, int option, int64_t value);
 /* Pre-filter counters since the last reset (counted only while HNM_OPT_STATS is 1): out[0]
  * rows scored, out[1] candidates re-scored in fp32, out[2] rows that took the exact fallback
- * scan.  Synchronizes the whole DEVICE (not the ctx stream), so it may be called on a ctx
+ * scan.  The sample-threshold path of hnm_dot_topk_f32 (pre-filter off, >= 8,192 items) counts
+ * the same way: its rows, the candidates its select kernel ranks, the rows whose candidate buffer
+ * overflowed (or held fewer than k) and took the LIST fallback.  Synchronizes the whole DEVICE (not the ctx stream), so it may be called on a ctx
  * another thread owns; counts of calls that thread issues while this runs may land before or
  * after a reset (totals are exact for threads that are idle meanwhile). */
 hnm_status hnm_ctx_prefilter_stats(hnm_ctx* ctx, int64_t* out, int reset);
@@ -269,7 +271,9 @@ hnm_status hnm_ncf_topk_f32(hnm_ctx* ctx, const hnm_ncf_weights* w, const int64_
  * (real score units; -inf when unknown, e.g. with the pre-filter off).  The caller may
  * replace the bounds by any valid lower bounds -- the max over the item shards of a node --
  * then finish completes the fused top-k with them; short_ok = 1 lets a row keep fewer than
- * k entries (padded with -inf / -1: another shard holds its better items).  Nothing else may
+ * k entries (padded with -inf / -1: another shard holds its better items): the row is then a
+ * prefix of its exact top-k that holds every item scoring at or above the row's bound, and (when
+ * out_val is given) nothing below it unless the row took the exact fallback scan.  Nothing else may
  * use the ctx between begin and finish (HNM_EINVAL otherwise). */
 hnm_status hnm_ncf_topk_begin_f32(hnm_ctx* ctx, const hnm_ncf_weights* w,
                                   const int64_t* user_ids, int64_t B, const int64_t* mask_ptr,
