@@ -172,6 +172,11 @@ _SIGS = {
     "hnm_itemcf_topk_f32": (_i32, [_p, _p, _p, _i64, C.c_int, _p, _p, _i64, _p, _i64, _p, _p,
                                    C.c_int, _p, _p]),
     "hnm_itemcf_route": (_i32, [_p, C.c_int, _i64, C.POINTER(C.c_int)]),
+    # ctx, tab, rows, ld, d, out [d, d]
+    "hnm_als_gram_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p]),
+    # ctx, ptr, idx, n_rows, tab, tab_rows, ld, d, gram, alpha, reg, row_ids, B, out, ldo
+    "hnm_als_solve_rows_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _f32, _f32, _p,
+                                      _i64, _p, _i64]),
 }
 
 _lib = None

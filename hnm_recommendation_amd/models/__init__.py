@@ -5,7 +5,8 @@ from .neural_cf import NeuralCF
 from .popularity import PopularityBaseline
 from .base import UserHistory
 from .item_cf import ItemCF
+from .implicit_als import ImplicitALS
 from .wide_deep import WideDeep
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
-           "ItemCF", "UserHistory"]
+           "ItemCF", "ImplicitALS", "UserHistory"]

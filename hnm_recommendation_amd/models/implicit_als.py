@@ -1,0 +1,270 @@
+"""ImplicitALS: matrix-factorization embeddings fitted on the GPU by alternating least squares
+for implicit feedback (Hu, Koren & Volinsky 2008).  No reference module: `GEMINI.md` stage 3
+names "Matrix Factorization (e.g. ALS ...)" beside the baselines, `src/models` never built it.
+
+    L(X, Y) = sum_{u,i} c_ui (p_ui - x_u . y_i)^2 + reg (|X|^2 + |Y|^2)
+    p_ui = 1, c_ui = 1 + alpha for (u, i) in the history; p_ui = 0, c_ui = 1 otherwise
+
+Two HIP entries (`csrc/als.hip`, contract in `include/hnm.h`):
+
+* `hnm_als_gram_f32` -- G = T^T T of a factor table, fixed-order chunked summation;
+* `hnm_als_solve_rows_f32` -- one half-step: per CSR row the d x d system
+  (G + alpha sum t t^T + reg I) x = (1 + alpha) sum t, by Cholesky in LDS.  The user step, the
+  item step (over the transposed history), fold-in of a basket (`user_factors`) and
+  `refresh_users` are this one entry, so they agree bit for bit.
+
+A fit is `iterations` sweeps (user step, then item step): no optimizer, no sampling, no
+learning rate.  The module IS a `MatrixFactorization` with zero biases: the same parameters and
+state_dict keys, served by the same certified dot-product top-K; a saved ImplicitALS loads as a
+MatrixFactorization and the reverse.
+"""
+from __future__ import annotations
+
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .base import UserHistory, dense_topk, empty_topk, f32c
+from .item_cf import ItemCF
+from .matrix_factorization import MatrixFactorization
+
+LOSS_PAIR_CHUNK = 1 << 20   # history pairs per float64 pass of loss()
+
+
+def supported_dim(d: int) -> bool:
+    return 16 <= d <= 128 and d % 16 == 0
+
+
+class ImplicitALS(MatrixFactorization):
+    def __init__(self, num_users: int, num_items: int, embedding_dim: int = 64,
+                 regularization: float = 0.01, alpha: float = 40.0, iterations: int = 15,
+                 seed: int = 0, top_k: int = 12):
+        if not supported_dim(int(embedding_dim)):
+            raise ValueError("embedding_dim must be a multiple of 16 in [16, 128]")
+        if not float(regularization) > 0.0 or not np.isfinite(regularization):
+            raise ValueError("regularization must be finite and > 0")
+        if not float(alpha) >= 0.0 or not np.isfinite(alpha):
+            raise ValueError("alpha must be finite and >= 0")
+        if int(iterations) < 0:
+            raise ValueError("iterations must be >= 0")
+        super().__init__(int(num_users), int(num_items), embedding_dim=int(embedding_dim),
+                         top_k=int(top_k), sparse=False)
+        self.save_hyperparameters()
+        self.regularization, self.alpha = float(regularization), float(alpha)
+        self.iterations, self.seed = int(iterations), int(seed)
+        self.history: Optional[UserHistory] = None
+        self.loss_history: List[float] = []
+        self._gram: Optional[torch.Tensor] = None   # Y^T Y of the fitted item table (fold-in)
+        with torch.no_grad():
+            self.user_embeddings.weight.zero_()
+            self._init_items()
+
+    def _init_items(self):
+        """Y ~ N(0, 0.01^2) from a CPU generator: the starting bits do not depend on the device."""
+        g = torch.Generator(device="cpu").manual_seed(self.seed)
+        y = torch.empty(self.num_items, self.embedding_dim, dtype=torch.float32)
+        y.normal_(0.0, 0.01, generator=g)
+        w = self.item_embeddings.weight
+        w.data.copy_(y.to(w.device))
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        out = super().load_state_dict(state_dict, *args, **kwargs)
+        self._gram = None
+        return out
+
+    _basket_csr = ItemCF._basket_csr   # the same validation of a list of baskets / a (ptr, idx) CSR
+    set_history = ItemCF.set_history
+
+    # ------------------------------------------------------------------ the two entries
+    def _tables(self):
+        """(X, Y): the embedding tables themselves as fp32 contiguous device tensors."""
+        for emb in (self.user_embeddings, self.item_embeddings):
+            w = emb.weight
+            if w.dtype != torch.float32 or not w.is_contiguous():
+                w.data = w.data.to(torch.float32).contiguous()
+        X, Y = self.user_embeddings.weight.data, self.item_embeddings.weight.data
+        _lib.require_gpu(X, Y)
+        return X, Y
+
+    def _gram_of(self, tab: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        d = self.embedding_dim
+        if out is None:
+            out = torch.empty(d, d, dtype=torch.float32, device=tab.device)
+        _lib.check(_lib.fn("hnm_als_gram_f32")(_lib.ctx(tab.device), _lib.ptr(tab), tab.shape[0],
+                                               tab.stride(0), d, _lib.ptr(out)),
+                   "hnm_als_gram_f32")
+        return out
+
+    def _solve(self, ptr, idx, n_rows: int, tab, gram, row_ids, B: int, out):
+        _lib.check(_lib.fn("hnm_als_solve_rows_f32")(
+            _lib.ctx(tab.device), _lib.ptr(ptr), _lib.ptr(idx), n_rows, _lib.ptr(tab),
+            tab.shape[0], tab.stride(0), self.embedding_dim, _lib.ptr(gram), self.alpha,
+            self.regularization, _lib.ptr(row_ids), B, _lib.ptr(out),
+            out.stride(0) if B else self.embedding_dim), "hnm_als_solve_rows_f32")
+        return out
+
+    def _item_gram(self) -> torch.Tensor:
+        _, Y = self._tables()
+        if self._gram is None or self._gram.device != Y.device:
+            self._gram = self._gram_of(Y)
+        return self._gram
+
+    # ------------------------------------------------------------------ fitting
+    @staticmethod
+    def _transpose(history: UserHistory):
+        """(tptr int64 [I + 1], tusers int32): the item -> user CSR, rows ascending by user id
+        (a stable sort by item id of pairs that are stored user-major)."""
+        dev, nnz = history.device, history.nnz
+        lens = history.hist_ptr[1:] - history.hist_ptr[:-1]
+        users = torch.repeat_interleave(torch.arange(history.num_users, device=dev), lens)
+        items = history.hist_idx[:nnz].to(torch.int64)
+        order = torch.sort(items, stable=True).indices
+        tptr = torch.zeros(history.num_items + 1, dtype=torch.int64, device=dev)
+        tptr[1:] = torch.cumsum(torch.bincount(items, minlength=history.num_items), 0)
+        tusers = users[order].to(torch.int32)
+        if nnz == 0:
+            tusers = torch.zeros(1, dtype=torch.int32, device=dev)
+        return tptr, tusers.contiguous()
+
+    def fit_history(self, history: UserHistory, *, iterations: Optional[int] = None,
+                    track_loss: bool = False):
+        """Fit on a `UserHistory` and keep it as the model's history: `iterations` sweeps of
+        (user step, item step) from the seeded Y.  `track_loss`: `loss()` after every sweep in
+        `self.loss_history` (a monitoring pass in float64 per sweep)."""
+        _lib.require_gpu(self.item_embeddings.weight)
+        iters = self.iterations if iterations is None else int(iterations)
+        if iters < 0:
+            raise ValueError("iterations must be >= 0")
+        self.set_history(history)
+        X, Y = self._tables()
+        dev = X.device
+        if history.device != dev:
+            raise ValueError(f"history lives on {history.device}, the model on {dev}")
+        with torch.no_grad():
+            self._init_items()
+            X.zero_()
+            self.user_bias.weight.zero_()
+            self.item_bias.weight.zero_()
+            self.global_bias.zero_()
+        self._gram = None
+        self.loss_history = []
+        tptr, tusers = self._transpose(history)
+        U, I = self.num_users, self.num_items
+        gram = torch.empty(self.embedding_dim, self.embedding_dim, dtype=torch.float32, device=dev)
+        for _ in range(iters):
+            self._gram_of(Y, gram)
+            self._solve(history.hist_ptr, history.hist_idx, U, Y, gram, None, U, X)
+            self._gram_of(X, gram)
+            self._solve(tptr, tusers, I, X, gram, None, I, Y)
+            if track_loss:
+                self.loss_history.append(self.loss())
+        _lib.sync_check(dev)
+        return self
+
+    def fit_interactions(self, user_ids, item_ids, *, iterations: Optional[int] = None,
+                         track_loss: bool = False):
+        """Fit from (user, item) interaction arrays or tensors (duplicates allowed; ids out of
+        range raise IndexError): builds the `UserHistory`, keeps it, runs the sweeps."""
+        _lib.require_gpu(self.item_embeddings.weight)
+        u = user_ids.detach().cpu().numpy() if isinstance(user_ids, torch.Tensor) else user_ids
+        i = item_ids.detach().cpu().numpy() if isinstance(item_ids, torch.Tensor) else item_ids
+        hist = UserHistory.from_interactions(np.asarray(u).reshape(-1), np.asarray(i).reshape(-1),
+                                             self.num_users, self.num_items, self.device)
+        return self.fit_history(hist, iterations=iterations, track_loss=track_loss)
+
+    def _need_history(self, history: Optional[UserHistory] = None) -> UserHistory:
+        h = self.history if history is None else history
+        if h is None:
+            raise RuntimeError("no history: call fit_interactions / fit_history / set_history")
+        if not isinstance(h, UserHistory):
+            raise TypeError("history must be a UserHistory")
+        if h.num_items != self.num_items or h.num_users != self.num_users:
+            raise ValueError(f"history built for {h.num_users} users x {h.num_items} items, "
+                             f"model has {self.num_users} x {self.num_items}")
+        if h.device != self.device:
+            raise ValueError(f"history lives on {h.device}, the model on {self.device}")
+        return h
+
+    def loss(self) -> float:
+        """L(X, Y) over the model's history in float64, without a [U, I] matrix:
+        sum_{u,i} (x_u . y_i)^2 = tr((X^T X)(Y^T Y)); each history pair then trades its s^2 for
+        (1 + alpha)(1 - s)^2; plus the regulariser."""
+        X, Y = self._tables()
+        h = self._need_history()
+        X64, Y64 = X.to(torch.float64), Y.to(torch.float64)
+        total = ((X64.T @ X64) * (Y64.T @ Y64)).sum()
+        lens = h.hist_ptr[1:] - h.hist_ptr[:-1]
+        users = torch.repeat_interleave(torch.arange(h.num_users, device=X.device), lens)
+        items = h.hist_idx[:h.nnz].to(torch.int64)
+        for p0 in range(0, h.nnz, LOSS_PAIR_CHUNK):
+            s = (X64[users[p0:p0 + LOSS_PAIR_CHUNK]] * Y64[items[p0:p0 + LOSS_PAIR_CHUNK]]).sum(1)
+            total = total + ((1.0 + self.alpha) * (1.0 - s) ** 2 - s ** 2).sum()
+        total = total + self.regularization * ((X64 ** 2).sum() + (Y64 ** 2).sum())
+        return float(total)
+
+    # ------------------------------------------------------------------ fold-in
+    def user_factors(self, baskets) -> torch.Tensor:
+        """[n, d] fold-in vectors of n baskets (a list of item-id iterables, or a (ptr, idx) CSR
+        with ascending unique rows): the user half-step against the fitted Y."""
+        gram = self._item_gram()
+        _, Y = self._tables()
+        ptr, idx, n = self._basket_csr(baskets)
+        out = torch.empty(n, self.embedding_dim, dtype=torch.float32, device=Y.device)
+        self._solve(ptr, idx, n, Y, gram, None, n, out)
+        _lib.sync_check(Y.device)   # a CSR given by the caller may hold any id
+        return out
+
+    def recommend_for_items(self, baskets, filter_seen: bool = True, k: Optional[int] = None):
+        """(scores [n, k], items [n, k]) for n baskets of item ids -- visitors without a user
+        index: the fold-in vectors are the user table of the dot-product top-K.
+        `filter_seen` removes each basket's own items from its answer."""
+        k = self.top_k if k is None else k
+        gram = self._item_gram()
+        _, Y = self._tables()
+        dev, d = Y.device, self.embedding_dim
+        ptr, idx, n = self._basket_csr(baskets)
+        kk = min(k, self.num_items)
+        if kk <= 0:
+            return empty_topk(k, ptr[:n])
+        if n == 0:
+            return (torch.empty(0, kk, dtype=torch.float32, device=dev),
+                    torch.empty(0, kk, dtype=torch.int64, device=dev))
+        F = torch.empty(n, d, dtype=torch.float32, device=dev)
+        self._solve(ptr, idx, n, Y, gram, None, n, F)
+        rows = torch.arange(n, dtype=torch.int64, device=dev)
+        ub = torch.zeros(n, dtype=torch.float32, device=dev)
+        ib, gb = f32c(self.item_bias.weight).reshape(-1), f32c(self.global_bias)
+        mptr, midx = (ptr, idx) if filter_seen else (None, None)
+        c = _lib.ctx(dev)
+        if kk > 64:
+            s = torch.empty(n, self.num_items, dtype=torch.float32, device=dev)
+            _lib.check(_lib.fn("hnm_dot_scores_f32")(
+                c, _lib.ptr(F), n, d, _lib.ptr(rows), n, _lib.ptr(Y), self.num_items, d, d,
+                _lib.ptr(ub), _lib.ptr(ib), _lib.ptr(gb), _lib.ptr(s), s.stride(0)),
+                "hnm_dot_scores_f32")
+            out = dense_topk(s, kk, mptr, midx)
+        else:
+            out_v = torch.empty(n, kk, dtype=torch.float32, device=dev)
+            out_i = torch.empty(n, kk, dtype=torch.int64, device=dev)
+            _lib.check(_lib.fn("hnm_dot_topk_f32")(
+                c, _lib.ptr(F), n, d, _lib.ptr(rows), n, _lib.ptr(Y), self.num_items, d, d,
+                _lib.ptr(ub), _lib.ptr(ib), _lib.ptr(gb), _lib.ptr(mptr), _lib.ptr(midx), kk,
+                _lib.ptr(out_v), _lib.ptr(out_i)), "hnm_dot_topk_f32")
+            out = (out_v, out_i)
+        _lib.sync_check(dev)
+        return out
+
+    def refresh_users(self, user_ids, history: Optional[UserHistory] = None):
+        """Recompute the stored factors of `user_ids` from `history` (default: the model's own)
+        against the fitted Y -- a customer who bought something since the fit, without a refit."""
+        h = self._need_history(history)
+        u, _ = self._ids(user_ids, self.num_users)
+        gram = self._item_gram()
+        X, Y = self._tables()
+        out = torch.empty(u.numel(), self.embedding_dim, dtype=torch.float32, device=Y.device)
+        self._solve(h.hist_ptr, h.hist_idx, self.num_users, Y, gram, u, u.numel(), out)
+        _lib.sync_check(Y.device)
+        X[u] = out
+        return self

@@ -25,6 +25,9 @@ article-metadata tables (out of scope: SURVEY §2):
   fitted `ItemCF` under "item_cf", and the answer for a visitor without a user index (a basket
   of item ids).  ItemCF rows that run out of co-bought items are back-filled from the
   popularity baseline when one is registered.
+* `Recommender.add_als` -- no reference counterpart: an `ImplicitALS` fitted on the transactions
+  under "implicit_als"; it answers users like every embedding model and baskets by fold-in
+  (`get_recommendations_for_items(model_name="implicit_als")`; its rows are full: no back-fill).
 """
 from __future__ import annotations
 
@@ -36,8 +39,8 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import torch
 
-from .models import (ItemCF, LightGCN, MatrixFactorization, NeuralCF, PopularityBaseline,
-                     WideDeep)
+from .models import (ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
+                     PopularityBaseline, WideDeep)
 from .models.base import UserHistory
 
 logger = logging.getLogger(__name__)
@@ -47,10 +50,12 @@ MAX_NUM_ITEMS = 100
 
 BASELINE = "popularity_baseline"  # serve.py:273: the name the reference registers it under
 ITEM_CF = "item_cf"
+ALS = "implicit_als"
 
 # serve.py:238-248, tested in this order
 _DISPATCH = (("matrix_factorization", MatrixFactorization), ("neural_cf", NeuralCF),
-             ("wide_deep", WideDeep), ("lightgcn", LightGCN), (ITEM_CF, ItemCF))
+             ("wide_deep", WideDeep), ("lightgcn", LightGCN), (ITEM_CF, ItemCF),
+             (ALS, ImplicitALS))
 
 
 def load_checkpoint(path: str, device="cpu") -> Dict:
@@ -144,6 +149,17 @@ class Recommender:
         model = ItemCF(self.num_users, self.num_items, **kw).to(self.device)
         model.fit_interactions(user_ids, item_ids)
         self.add_model(ITEM_CF, model)
+        if not self.user_history and self._history_dev is None:
+            self._history_dev = model.history
+        return model
+
+    def add_als(self, user_ids, item_ids, **kw) -> ImplicitALS:
+        """Fit an `ImplicitALS` (keywords: embedding_dim, regularization, alpha, iterations,
+        seed, top_k) on the transactions' (user, item) pairs and register it as "implicit_als".
+        Its history becomes the recommender's device history when the recommender has none."""
+        model = ImplicitALS(self.num_users, self.num_items, **kw).to(self.device)
+        model.fit_interactions(user_ids, item_ids)
+        self.add_model(ALS, model)
         if not self.user_history and self._history_dev is None:
             self._history_dev = model.history
         return model
@@ -290,7 +306,7 @@ class Recommender:
         that cannot answer from items, or an item outside [0, num_items)."""
         self._check_num_items(num_items)
         name, model = self._resolve_model(model_name)
-        if not isinstance(model, ItemCF):
+        if not isinstance(model, (ItemCF, ImplicitALS)):
             raise ValueError(f"model {name} cannot answer from a basket of items")
         basket = sorted({int(i) for i in item_ids})
         if basket and not 0 <= basket[0] <= basket[-1] < self.num_items:
@@ -298,6 +314,11 @@ class Recommender:
         with torch.no_grad():
             vals, items = model.recommend_for_items([basket], filter_seen=True, k=num_items)
         vals, items = vals.cpu().tolist(), items.cpu().tolist()
+        if isinstance(model, ImplicitALS):
+            # every row is full: nothing to back-fill; a basket that leaves fewer than num_items
+            # items ends in masked entries at -inf (the dot top-K's convention): not listed
+            n = next((j for j, v in enumerate(vals[0]) if v == float("-inf")), len(vals[0]))
+            return self._result(None, name, vals[0][:n], items[0][:n], include_scores)
 
         def fill(rows):
             with torch.no_grad():

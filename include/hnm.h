@@ -743,6 +743,44 @@ hnm_status hnm_itemcf_topk_f32(hnm_ctx* ctx, const int32_t* nbr_idx, const float
  * N neighbours per item; 1: the dense route.  No launch, no sync. */
 hnm_status hnm_itemcf_route(hnm_ctx* ctx, int N, int64_t history_len, int* route);
 
+/* ---- ImplicitALS: alternating least squares for implicit feedback (Hu, Koren & Volinsky
+ * 2008; no reference counterpart) ----------------------------------------------------------
+ * Gram matrix.  out f32[d, d] (contiguous) = tab^T tab over the first `rows` rows of tab (row
+ * stride ld >= d), all in fp32: rows are taken in chunks of 2,048; inside a chunk entry (i, j)
+ * is the fmaf chain acc = fmaf(t_r[i], t_r[j], acc) over the chunk's rows r in ascending order
+ * from 0.0f; the chunk partials are added in ascending chunk order from the first partial.
+ * Chunk size and order are compile-time constants, so the result is the same bits on every run
+ * and does not depend on the grid or the CU count; out is exactly symmetric.  rows = 0: zeros.
+ * Workspace: cdiv(rows, 2048) * d * d floats of the ctx workspace (22 MB for 1,371,980 rows at
+ * d = 64, 88 MB at d = 128).  d: a multiple of 16 in [16, 128], else HNM_EUNSUPPORTED. */
+hnm_status hnm_als_gram_f32(hnm_ctx* ctx, const float* tab, int64_t rows, int64_t ld, int64_t d,
+                            float* out);
+/* One ALS half-step for B rows of a CSR.  ptr int64[n_rows + 1] / idx int32: the CSR (rows of
+ * UserHistory's layout, or of its transpose); tab f32[tab_rows, d] (row stride ld >= d): the
+ * table the rows index; gram f32[d, d]: hnm_als_gram_f32 of tab.  Output row b (out + b * ldo,
+ * ldo >= d) is the solution for CSR row row_ids[b] (int64[B]), or for row b when row_ids is
+ * NULL (then B <= n_rows).  For a row with entries j_0, j_1, ... (stored order), in fp32:
+ *   S[i][c] = fmaf chain over m of t_{j_m}[i] * t_{j_m}[c], from 0.0f
+ *   b0[c]   = ((0 + t_{j_0}[c]) + t_{j_1}[c]) + ...
+ *   A[i][c] = fmaf(alpha, S[i][c], gram[i][c]) (+ reg when i == c),  c <= i
+ *   b[c]    = (1.0f + alpha) * b0[c]
+ *   out     = A^-1 b by a right-looking Cholesky A = L L^T (l_kk = sqrtf(a_kk), l_ik = a_ik /
+ *             l_kk, a_ij = fmaf(-l_ik, l_jk, a_ij)), b carried as an extra row (L y = b), then
+ *             L^T x = y from the last entry up (x_k = y_k / l_kk, y_i = fmaf(-l_ki, x_k, y_i)).
+ * Only the lower triangle of gram is read.  A row without entries gives exact zeros.  One
+ * definition serves the fit and fold-in, and one workgroup owns a row whatever its length (a
+ * long row is the same loop run longer: there is no length threshold and no second route), so a
+ * row's bits depend on its inputs alone -- not on B, on the other rows or on the run.  No
+ * floating-point atomics.  An idx entry outside [0, tab_rows) or a row_ids entry outside
+ * [0, n_rows) raises the ctx error word (HNM_EOOB from hnm_ctx_check) and that output row is
+ * NaN; the other rows are unaffected.  d: a multiple of 16 in [16, 128], else
+ * HNM_EUNSUPPORTED; reg <= 0, alpha < 0 or a non-finite value: HNM_EINVAL.  B = 0 or
+ * n_rows = 0: HNM_OK, nothing launched.  Workspace: none (the systems live in LDS). */
+hnm_status hnm_als_solve_rows_f32(hnm_ctx* ctx, const int64_t* ptr, const int32_t* idx,
+                                  int64_t n_rows, const float* tab, int64_t tab_rows, int64_t ld,
+                                  int64_t d, const float* gram, float alpha, float reg,
+                                  const int64_t* row_ids, int64_t B, float* out, int64_t ldo);
+
 #ifdef __cplusplus
 }
 #endif
