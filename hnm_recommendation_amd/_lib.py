@@ -177,6 +177,9 @@ _SIGS = {
     # ctx, ptr, idx, n_rows, tab, tab_rows, ld, d, gram, alpha, reg, row_ids, B, out, ldo
     "hnm_als_solve_rows_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _f32, _f32, _p,
                                       _i64, _p, _i64]),
+    # ctx, ptr, idx, w, n_rows, tab, tab_rows, ld, d, gram, alpha, reg, row_ids, B, out, ldo
+    "hnm_als_solve_rows_weighted_f32": (_i32, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p,
+                                               _f32, _f32, _p, _i64, _p, _i64]),
 }
 
 _lib = None

@@ -32,6 +32,17 @@
 // four rows a wave in flight, indices prefetched two images ahead) took 116.7 / 1,144 ms: 73
 // instead of 56 VGPR at d = 64 cost more occupancy than the barriers it saved.
 //
+// Weighted half-step (hnm_als_solve_rows_weighted_f32; als_solve_kernel<NT, true>): a weight w_j
+// per stored entry, c = 1 + alpha w, p = 1:
+//   S  = sum w_j t_j t_j^T  (fl(w_j t_j[i]) * t_j[c] in the chain: the weight scales the MFMA's A
+//        operand, the one indexed by the output row)
+//   b0 = sum t_j (as above)    bw = fmaf chain of w_j t_j    b = fma(alpha, bw, b0)
+// and everything from A on is the code above.  With every weight 1 (or 2^e) the result is
+// bitwise the unweighted one at alpha (or 2^e alpha) when 1 + alpha is exact in fp32.  The
+// unweighted instantiation is unchanged: the same registers and LDS as before the template
+// parameter (56 VGPR at d = 64); the weighted one takes 64 there (six instead of seven waves a
+// SIMD), which is its measured cost at d = 64.
+//
 // Gram.  Workgroup c sums rows [c * ALS_GRAM_ROWS, (c + 1) * ALS_GRAM_ROWS) through the same
 // image + MFMA loop and writes its lower triangle to the ctx workspace; a second kernel adds
 // the chunk partials in ascending chunk order and mirrors the result.  Chunk size and order are
@@ -55,8 +66,11 @@ __device__ __forceinline__ void als_tile(int q, int& ti, int& tj) {
 }
 
 // acc[s] += image^T image restricted to this wave's tiles, rows [0, n) of the image in order.
-template <int NT>
-__device__ __forceinline__ void als_mfma_chunk(const float* img, int n, f32x16 (&acc)[ALS_MAX_TILES]) {
+// WEIGHTED: image^T diag(ws) image, the weight of image row k applied to the operand indexed by
+// the output row (the MFMA's A operand) as it is read: fl(ws[k] * t_k[i]) * t_k[c].
+template <int NT, bool WEIGHTED = false>
+__device__ __forceinline__ void als_mfma_chunk(const float* img, int n, f32x16 (&acc)[ALS_MAX_TILES],
+                                               const float* ws = nullptr) {
   constexpr int DP = 32 * NT, NTILES = NT * (NT + 1) / 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int kh = lane >> 5, c = lane & 31;
@@ -68,16 +82,28 @@ __device__ __forceinline__ void als_mfma_chunk(const float* img, int n, f32x16 (
       als_tile(q, ti, tj);
       const float* pa = img + kh * DP + 32 * ti + c;
       const float* pb = img + kh * DP + 32 * tj + c;
-      for (int k = 0; k < n; k += 2)  // rows past n are zero: fma(0, 0, x) = x
-        acc[s] = mfma32x32x2(pa[k * DP], pb[k * DP], acc[s]);
+      if constexpr (WEIGHTED) {
+        const float* pw = ws + kh;
+        for (int k = 0; k < n; k += 2)  // rows past n are zero, and so are their weights
+          acc[s] = mfma32x32x2(pw[k] * pa[k * DP], pb[k * DP], acc[s]);
+      } else {
+        for (int k = 0; k < n; k += 2)  // rows past n are zero: fma(0, 0, x) = x
+          acc[s] = mfma32x32x2(pa[k * DP], pb[k * DP], acc[s]);
+      }
     }
   }
 }
 
 // ------------------------------------------------------------------ solve
-template <int NT>
+// WEIGHTED (hnm_als_solve_rows_weighted_f32): wgt holds one weight per idx entry; an image's 32
+// weights travel with its 32 indices (prefetched the same way) into `ws`, the MFMA loop scales
+// its row-side operand by them, and the b0 chain and bw = sum w t run side by side on the last
+// wave (d <= 64) or the last two.  The unweighted
+// instantiation is the code it was: `ws`, `badw` and every weighted statement compile away.
+template <int NT, bool WEIGHTED>
 __global__ __launch_bounds__(256) void als_solve_kernel(
-    const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx, int64_t n_rows,
+    const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+    const float* __restrict__ wgt, int64_t n_rows,
     const float* __restrict__ tab, int64_t tab_rows, int64_t ld, int d,
     const float* __restrict__ gram, float alpha, float one_alpha, float reg,
     const int64_t* __restrict__ row_ids, float* __restrict__ out, int64_t ldo, unsigned* err) {
@@ -86,6 +112,8 @@ __global__ __launch_bounds__(256) void als_solve_kernel(
   __shared__ float As[LD * LD];  // rows 0 .. d of the augmented matrix; first the gather image
   __shared__ float piv[DP];
   __shared__ int bad;
+  __shared__ float ws[ALS_CHUNK];  // WEIGHTED: the image rows' weights, zero past the row's end
+  __shared__ int badw;             // WEIGHTED: a negative or non-finite weight was loaded
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int64_t b = blockIdx.x;
   float* orow = out + b * ldo;
@@ -102,19 +130,38 @@ __global__ __launch_bounds__(256) void als_solve_kernel(
     return;
   }
   if (t == 0) bad = 0;
+  if constexpr (WEIGHTED) {
+    if (t == 0) badw = 0;
+  }
   f32x16 acc[ALS_MAX_TILES];
 #pragma unroll
   for (int s = 0; s < ALS_MAX_TILES; ++s)
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[s][q] = 0.f;
   float bsum = 0.f;
+  float bw = 0.f;  // WEIGHTED: the fmaf chain of w t
+  // WEIGHTED: column bc of b0 and bw belongs to thread BT0 + bc -- the last wave at d <= 64, the
+  // last two above: the waves with the fewest MFMA tiles (none at d <= 64), where the unweighted
+  // kernel's threads c < d sit on the waves with the most.  Which thread runs a chain does not
+  // show in its bits.
+  constexpr int BT0 = 256 - 64 * ((NT + 1) / 2);
+  const int bc = t - BT0;
   // this thread's EPT elements of the image of rows [c0, c0 + ALS_CHUNK) of the CSR row, held in
   // registers: the next image is in flight under this one's MFMAs
   constexpr int EPT = ALS_CHUNK * DP / 256;
   float v[EPT];
   bool mybad = false;
+  float wv = 0.f;  // WEIGHTED: thread k < ALS_CHUNK holds the weight of image row k (checked when
+                   // it goes to LDS)
+  bool mybadw = false;
   auto gather = [&](int64_t c0) {
     const int n = (int)std::min<int64_t>(ALS_CHUNK, h - c0);
+    if constexpr (WEIGHTED) {
+      // issued with the image's first index load and not looked at here: a test of the value
+      // would wait out a whole memory latency of its own (the weights stream, one new line an
+      // image), which the long rows of the item step pay once per image
+      if (t < ALS_CHUNK) wv = t < n ? wgt[p0 + c0 + t] : 0.f;
+    }
 #pragma unroll
     for (int q = 0; q < EPT; ++q) {
       const int e = t + 256 * q, k = e / DP, c = e % DP;
@@ -133,18 +180,46 @@ __global__ __launch_bounds__(256) void als_solve_kernel(
     __syncthreads();  // the previous image has been read (and `bad` is initialised)
 #pragma unroll
     for (int q = 0; q < EPT; ++q) As[t + 256 * q] = v[q];
+    if constexpr (WEIGHTED) {
+      if (t < ALS_CHUNK) {
+        if (!(wv >= 0.f && wv < __builtin_inff())) mybadw = true;  // negative, inf or NaN
+        ws[t] = wv;
+      }
+    }
     __syncthreads();
     if (c0 + ALS_CHUNK < h) gather(c0 + ALS_CHUNK);
-    als_mfma_chunk<NT>(As, n, acc);
-    if (t < d)
-      for (int k = 0; k < n; ++k) bsum += As[k * DP + t];
+    als_mfma_chunk<NT, WEIGHTED>(As, n, acc, ws);
+    if constexpr (WEIGHTED) {
+      if (bc >= 0 && bc < d) {
+#pragma unroll 4  // deeper unrolls cost VGPRs: at d = 64 this one stays at 64 (6 waves a SIMD)
+        for (int k = 0; k < n; ++k) {
+          const float x = As[k * DP + bc];
+          bsum += x;
+          bw = fmaf(ws[k], x, bw);
+        }
+      }
+    } else {
+      if (t < d)
+        for (int k = 0; k < n; ++k) bsum += As[k * DP + t];
+    }
   }
   if (mybad) bad = 1;
+  if constexpr (WEIGHTED) {
+    if (mybadw) badw = 1;
+  }
   __syncthreads();  // the last image has been read: the matrix takes its place
-  if (bad) {        // uniform
-    if (t == 0) hnm_flag(err, HNM_ERR_OOB);
-    if (t < d) orow[t] = __builtin_nanf("");
-    return;
+  if constexpr (WEIGHTED) {
+    if (bad || badw) {  // uniform
+      if (t == 0) hnm_flag(err, (bad ? HNM_ERR_OOB : 0u) | (badw ? HNM_ERR_WEIGHT : 0u));
+      if (t < d) orow[t] = __builtin_nanf("");
+      return;
+    }
+  } else {
+    if (bad) {  // uniform
+      if (t == 0) hnm_flag(err, HNM_ERR_OOB);
+      if (t < d) orow[t] = __builtin_nanf("");
+      return;
+    }
   }
 #pragma unroll
   for (int s = 0; s < ALS_MAX_TILES; ++s) {
@@ -164,7 +239,11 @@ __global__ __launch_bounds__(256) void als_solve_kernel(
       }
     }
   }
-  if (t < d) As[d * LD + t] = one_alpha * bsum;
+  if constexpr (WEIGHTED) {
+    if (bc >= 0 && bc < d) As[d * LD + bc] = fmaf(alpha, bw, bsum);
+  } else {
+    if (t < d) As[d * LD + t] = one_alpha * bsum;
+  }
   __syncthreads();
   // right-looking Cholesky of rows 0 .. d (row d = b^T becomes y^T)
   for (int k = 0; k < d; ++k) {
@@ -291,11 +370,13 @@ extern "C" hnm_status hnm_als_gram_f32(hnm_ctx* ctx, const float* tab, int64_t r
   return HNM_OK;
 }
 
-extern "C" hnm_status hnm_als_solve_rows_f32(hnm_ctx* ctx, const int64_t* ptr, const int32_t* idx,
-                                             int64_t n_rows, const float* tab, int64_t tab_rows,
-                                             int64_t ld, int64_t d, const float* gram, float alpha,
-                                             float reg, const int64_t* row_ids, int64_t B,
-                                             float* out, int64_t ldo) {
+namespace {
+
+// The two solve entries: w == NULL and weighted == false is hnm_als_solve_rows_f32.
+hnm_status als_solve_rows(hnm_ctx* ctx, const int64_t* ptr, const int32_t* idx, const float* w,
+                          bool weighted, int64_t n_rows, const float* tab, int64_t tab_rows,
+                          int64_t ld, int64_t d, const float* gram, float alpha, float reg,
+                          const int64_t* row_ids, int64_t B, float* out, int64_t ldo) {
   HNM_CTX_DEVICE(ctx);
   HNM_REQUIRE(ctx, HNM_EINVAL, "als_solve_rows: ctx is NULL");
   HNM_REQUIRE(als_dim_ok(d), HNM_EUNSUPPORTED,
@@ -311,24 +392,56 @@ extern "C" hnm_status hnm_als_solve_rows_f32(hnm_ctx* ctx, const int64_t* ptr, c
   HNM_REQUIRE(ld >= d && ldo >= d, HNM_EINVAL, "als_solve_rows: ld or ldo < d");
   HNM_REQUIRE(ptr && idx && gram && out && (tab || tab_rows == 0), HNM_EINVAL,
               "als_solve_rows: NULL argument");
+  HNM_REQUIRE(w || !weighted, HNM_EINVAL, "als_solve_rows_weighted: w is NULL");
   HNM_REQUIRE(row_ids || B <= n_rows, HNM_EINVAL,
               "als_solve_rows: B > n_rows without row_ids");
   const int nt = (int)hnm_cdiv(d, 32);
   const dim3 grid((unsigned)B), block(256);
   const float one_alpha = 1.0f + alpha;
-#define ALS_SOLVE(NT)                                                                         \
-  hipLaunchKernelGGL(als_solve_kernel<NT>, grid, block, 0, ctx->stream, ptr, idx, n_rows, tab, \
-                     tab_rows, ld, (int)d, gram, alpha, one_alpha, reg, row_ids, out, ldo,    \
+#define ALS_SOLVE(NT, W)                                                                         \
+  hipLaunchKernelGGL((als_solve_kernel<NT, W>), grid, block, 0, ctx->stream, ptr, idx, w, n_rows, \
+                     tab, tab_rows, ld, (int)d, gram, alpha, one_alpha, reg, row_ids, out, ldo,   \
                      ctx->err_dev)
   hnm_timer_begin(ctx, HNM_TIME_SCORE);
-  switch (nt) {
-    case 1: ALS_SOLVE(1); break;
-    case 2: ALS_SOLVE(2); break;
-    case 3: ALS_SOLVE(3); break;
-    default: ALS_SOLVE(4); break;
+  if (weighted) {
+    switch (nt) {
+      case 1: ALS_SOLVE(1, true); break;
+      case 2: ALS_SOLVE(2, true); break;
+      case 3: ALS_SOLVE(3, true); break;
+      default: ALS_SOLVE(4, true); break;
+    }
+  } else {
+    switch (nt) {
+      case 1: ALS_SOLVE(1, false); break;
+      case 2: ALS_SOLVE(2, false); break;
+      case 3: ALS_SOLVE(3, false); break;
+      default: ALS_SOLVE(4, false); break;
+    }
   }
   hnm_timer_end(ctx, HNM_TIME_SCORE);
 #undef ALS_SOLVE
   HNM_LAUNCH_CHECK();
   return HNM_OK;
+}
+
+}  // namespace
+
+extern "C" hnm_status hnm_als_solve_rows_f32(hnm_ctx* ctx, const int64_t* ptr, const int32_t* idx,
+                                             int64_t n_rows, const float* tab, int64_t tab_rows,
+                                             int64_t ld, int64_t d, const float* gram, float alpha,
+                                             float reg, const int64_t* row_ids, int64_t B,
+                                             float* out, int64_t ldo) {
+  return als_solve_rows(ctx, ptr, idx, nullptr, false, n_rows, tab, tab_rows, ld, d, gram, alpha,
+                        reg, row_ids, B, out, ldo);
+}
+
+extern "C" hnm_status hnm_als_solve_rows_weighted_f32(hnm_ctx* ctx, const int64_t* ptr,
+                                                      const int32_t* idx, const float* w,
+                                                      int64_t n_rows, const float* tab,
+                                                      int64_t tab_rows, int64_t ld, int64_t d,
+                                                      const float* gram, float alpha, float reg,
+                                                      const int64_t* row_ids, int64_t B,
+                                                      float* out, int64_t ldo) {
+  return als_solve_rows(ctx, ptr, idx, w, true, n_rows, tab, tab_rows, ld, d, gram, alpha, reg,
+                        row_ids, B, out, ldo);
 }

@@ -308,6 +308,11 @@ extern "C" hnm_status hnm_ctx_check(hnm_ctx* ctx) {
                     "(rows were truncated)");
       return HNM_EINVAL;
     }
+    if (h & HNM_ERR_WEIGHT) {
+      hnm_set_error("hnm_als_solve_rows_weighted_f32: a negative or non-finite weight (those "
+                    "output rows are NaN)");
+      return HNM_EINVAL;
+    }
   }
   return HNM_OK;
 }

@@ -148,24 +148,49 @@ class UserHistory:
         self._set(full, idx, num_users, num_items, device)
 
     @classmethod
-    def from_interactions(cls, user_ids, item_ids, num_users: int, num_items: int, device):
+    def from_interactions(cls, user_ids, item_ids, num_users: int, num_items: int, device,
+                          weights=None):
         """From (user, item) interaction arrays -- e.g. the training transactions that are a
-        customer's purchase history (serve.py:166-168) -- de-duplicated and sorted per user."""
+        customer's purchase history (serve.py:166-168) -- de-duplicated and sorted per user.
+
+        `weights`: one finite weight >= 0 per transaction (a quantity, a recency decay, their
+        product; ValueError otherwise).  The weight of a distinct pair is the float64 sum of its
+        transactions' weights, taken in ascending weight order and then rounded to fp32, so a
+        permutation of the transactions gives the same bits: `hist_w`, an fp32 device tensor
+        aligned with `hist_idx` (None without `weights`).  Only ImplicitALS reads it."""
         u = np.asarray(user_ids, np.int64)
         i = np.asarray(item_ids, np.int64)
         if u.shape != i.shape:
             raise ValueError("user_ids and item_ids must have the same shape")
         if u.size and (u.min() < 0 or u.max() >= num_users or i.min() < 0 or i.max() >= num_items):
             raise IndexError("interaction ids out of range")
-        key = np.unique(u * num_items + i)
+        pair_w = None
+        if weights is None:
+            key = np.unique(u * num_items + i)
+        else:
+            if isinstance(weights, torch.Tensor):
+                weights = weights.detach().cpu().numpy()
+            w = np.asarray(weights, np.float64)
+            if w.shape != u.shape:
+                raise ValueError("weights must have the shape of user_ids")
+            if w.size and not (np.isfinite(w).all() and (w >= 0).all()):
+                raise ValueError("weights must be finite and >= 0")
+            k, w = (u * num_items + i).reshape(-1), w.reshape(-1)
+            order = np.lexsort((w, k))                    # by pair, then by ascending weight
+            k, w = k[order], w[order]
+            starts = np.nonzero(np.r_[True, k[1:] != k[:-1]])[0] if k.size else np.zeros(0, np.int64)
+            key = k[starts]
+            pair_w = (np.add.reduceat(w, starts) if k.size else w).astype(np.float32)
+            if not np.isfinite(pair_w).all():
+                raise ValueError("a pair's summed weight exceeds the fp32 range")
         r, items = np.divmod(key, num_items)
         full = np.zeros(int(num_users) + 1, np.int64)
         np.cumsum(np.bincount(r, minlength=num_users), out=full[1:])
         obj = cls.__new__(cls)
-        obj._set(full, items.astype(np.int32), num_users, num_items, device)
+        obj._set(full, items.astype(np.int32), num_users, num_items, device, pair_w)
         return obj
 
-    def _set(self, ptr, idx, num_users, num_items, device):
+    def _set(self, ptr, idx, num_users, num_items, device, w=None):
         self.num_users, self.num_items = int(num_users), int(num_items)
         dev = torch.device(device)
         if dev.type == "cuda" and dev.index is None:
@@ -176,6 +201,8 @@ class UserHistory:
         self.nnz = int(ptr[-1])
         self.hist_ptr = torch.from_numpy(ptr).to(self.device)
         self.hist_idx = torch.from_numpy(idx if idx.size else np.zeros(1, np.int32)).to(self.device)
+        self.hist_w = None if w is None else torch.from_numpy(
+            w if w.size else np.zeros(1, np.float32)).to(self.device)
 
     def mask_for(self, user_ids: torch.Tensor, item_range=None):
         """(mask_ptr int64[B+1], mask_idx int32) for a batch of device user ids -- with

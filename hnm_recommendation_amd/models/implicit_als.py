@@ -3,15 +3,24 @@ for implicit feedback (Hu, Koren & Volinsky 2008).  No reference module: `GEMINI
 names "Matrix Factorization (e.g. ALS ...)" beside the baselines, `src/models` never built it.
 
     L(X, Y) = sum_{u,i} c_ui (p_ui - x_u . y_i)^2 + reg (|X|^2 + |Y|^2)
-    p_ui = 1, c_ui = 1 + alpha for (u, i) in the history; p_ui = 0, c_ui = 1 otherwise
+    p_ui = 1, c_ui = 1 + alpha w_ui for (u, i) in the history; p_ui = 0, c_ui = 1 otherwise
 
-Two HIP entries (`csrc/als.hip`, contract in `include/hnm.h`):
+w_ui is the pair's weight in the history (`UserHistory.hist_w`: summed purchase counts, a recency
+decay, ...; the caller applies any log or other transform first), and 1 when the history carries
+no weights -- the model this module has always fitted, through the same entry and to the same
+bits.
+
+Three HIP entries (`csrc/als.hip`, contract in `include/hnm.h`):
 
 * `hnm_als_gram_f32` -- G = T^T T of a factor table, fixed-order chunked summation;
 * `hnm_als_solve_rows_f32` -- one half-step: per CSR row the d x d system
   (G + alpha sum t t^T + reg I) x = (1 + alpha) sum t, by Cholesky in LDS.  The user step, the
   item step (over the transposed history), fold-in of a basket (`user_factors`) and
-  `refresh_users` are this one entry, so they agree bit for bit.
+  `refresh_users` are this one entry, so they agree bit for bit;
+* `hnm_als_solve_rows_weighted_f32` -- the same half-step with a weight per stored entry:
+  (G + alpha sum w t t^T + reg I) x = sum (1 + alpha w) t.  A history with `hist_w` takes it in
+  the fit (the transpose carries the weights) and in `refresh_users`; `user_factors` and
+  `recommend_for_items` take it when the call gives `weights`.
 
 A fit is `iterations` sweeps (user step, then item step): no optimizer, no sampling, no
 learning rate.  The module IS a `MatrixFactorization` with zero biases: the same parameters and
@@ -77,7 +86,7 @@ class ImplicitALS(MatrixFactorization):
     _basket_csr = ItemCF._basket_csr   # the same validation of a list of baskets / a (ptr, idx) CSR
     set_history = ItemCF.set_history
 
-    # ------------------------------------------------------------------ the two entries
+    # ------------------------------------------------------------------ the entries
     def _tables(self):
         """(X, Y): the embedding tables themselves as fp32 contiguous device tensors."""
         for emb in (self.user_embeddings, self.item_embeddings):
@@ -97,12 +106,21 @@ class ImplicitALS(MatrixFactorization):
                    "hnm_als_gram_f32")
         return out
 
-    def _solve(self, ptr, idx, n_rows: int, tab, gram, row_ids, B: int, out):
-        _lib.check(_lib.fn("hnm_als_solve_rows_f32")(
-            _lib.ctx(tab.device), _lib.ptr(ptr), _lib.ptr(idx), n_rows, _lib.ptr(tab),
-            tab.shape[0], tab.stride(0), self.embedding_dim, _lib.ptr(gram), self.alpha,
-            self.regularization, _lib.ptr(row_ids), B, _lib.ptr(out),
-            out.stride(0) if B else self.embedding_dim), "hnm_als_solve_rows_f32")
+    def _solve(self, ptr, idx, n_rows: int, tab, gram, row_ids, B: int, out, w=None):
+        """One half-step; `w` (fp32, aligned with idx) selects the weighted entry."""
+        ldo = out.stride(0) if B else self.embedding_dim
+        if w is None:
+            _lib.check(_lib.fn("hnm_als_solve_rows_f32")(
+                _lib.ctx(tab.device), _lib.ptr(ptr), _lib.ptr(idx), n_rows, _lib.ptr(tab),
+                tab.shape[0], tab.stride(0), self.embedding_dim, _lib.ptr(gram), self.alpha,
+                self.regularization, _lib.ptr(row_ids), B, _lib.ptr(out), ldo),
+                "hnm_als_solve_rows_f32")
+        else:
+            _lib.check(_lib.fn("hnm_als_solve_rows_weighted_f32")(
+                _lib.ctx(tab.device), _lib.ptr(ptr), _lib.ptr(idx), _lib.ptr(w), n_rows,
+                _lib.ptr(tab), tab.shape[0], tab.stride(0), self.embedding_dim, _lib.ptr(gram),
+                self.alpha, self.regularization, _lib.ptr(row_ids), B, _lib.ptr(out), ldo),
+                "hnm_als_solve_rows_weighted_f32")
         return out
 
     def _item_gram(self) -> torch.Tensor:
@@ -114,8 +132,9 @@ class ImplicitALS(MatrixFactorization):
     # ------------------------------------------------------------------ fitting
     @staticmethod
     def _transpose(history: UserHistory):
-        """(tptr int64 [I + 1], tusers int32): the item -> user CSR, rows ascending by user id
-        (a stable sort by item id of pairs that are stored user-major)."""
+        """(tptr int64 [I + 1], tusers int32, tw fp32 or None): the item -> user CSR, rows
+        ascending by user id (a stable sort by item id of pairs that are stored user-major); the
+        history's weights, when it has them, go through the same permutation."""
         dev, nnz = history.device, history.nnz
         lens = history.hist_ptr[1:] - history.hist_ptr[:-1]
         users = torch.repeat_interleave(torch.arange(history.num_users, device=dev), lens)
@@ -126,13 +145,20 @@ class ImplicitALS(MatrixFactorization):
         tusers = users[order].to(torch.int32)
         if nnz == 0:
             tusers = torch.zeros(1, dtype=torch.int32, device=dev)
-        return tptr, tusers.contiguous()
+        tw = None
+        if history.hist_w is not None:
+            tw = history.hist_w[:nnz][order].contiguous()
+            if nnz == 0:
+                tw = torch.zeros(1, dtype=torch.float32, device=dev)
+        return tptr, tusers.contiguous(), tw
 
     def fit_history(self, history: UserHistory, *, iterations: Optional[int] = None,
                     track_loss: bool = False):
         """Fit on a `UserHistory` and keep it as the model's history: `iterations` sweeps of
-        (user step, item step) from the seeded Y.  `track_loss`: `loss()` after every sweep in
-        `self.loss_history` (a monitoring pass in float64 per sweep)."""
+        (user step, item step) from the seeded Y.  A history with weights (`hist_w`) is fitted
+        with c_ui = 1 + alpha w_ui through the weighted entry, one without through the unweighted
+        one.  `track_loss`: `loss()` after every sweep in `self.loss_history` (a monitoring pass
+        in float64 per sweep)."""
         _lib.require_gpu(self.item_embeddings.weight)
         iters = self.iterations if iterations is None else int(iterations)
         if iters < 0:
@@ -150,28 +176,69 @@ class ImplicitALS(MatrixFactorization):
             self.global_bias.zero_()
         self._gram = None
         self.loss_history = []
-        tptr, tusers = self._transpose(history)
+        tptr, tusers, tw = self._transpose(history)
         U, I = self.num_users, self.num_items
         gram = torch.empty(self.embedding_dim, self.embedding_dim, dtype=torch.float32, device=dev)
         for _ in range(iters):
             self._gram_of(Y, gram)
-            self._solve(history.hist_ptr, history.hist_idx, U, Y, gram, None, U, X)
+            self._solve(history.hist_ptr, history.hist_idx, U, Y, gram, None, U, X, history.hist_w)
             self._gram_of(X, gram)
-            self._solve(tptr, tusers, I, X, gram, None, I, Y)
+            self._solve(tptr, tusers, I, X, gram, None, I, Y, tw)
             if track_loss:
                 self.loss_history.append(self.loss())
         _lib.sync_check(dev)
         return self
 
-    def fit_interactions(self, user_ids, item_ids, *, iterations: Optional[int] = None,
+    @staticmethod
+    def _interaction_weights(n: int, weights, days_ago, time_decay: float):
+        """float64 [n] per-transaction weights, `weights` (default 1) times
+        exp(-time_decay * days_ago) (PopularityBaseline's convention), or None when neither
+        `weights` nor `days_ago` is given.  ValueError for a negative time_decay, fractional or
+        negative days, or a shape mismatch."""
+        time_decay = float(time_decay)
+        if not time_decay >= 0.0 or not np.isfinite(time_decay):
+            raise ValueError("time_decay must be finite and >= 0")
+        if weights is None and days_ago is None:
+            return None
+
+        def host(a, what):
+            a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+            a = a.reshape(-1)
+            if a.shape[0] != n:
+                raise ValueError(f"{what} must have one entry per interaction")
+            return a
+
+        w = np.ones(n, np.float64) if weights is None else host(weights, "weights").astype(np.float64)
+        if days_ago is not None:
+            days = host(days_ago, "days_ago")
+            if days.dtype.kind not in "iu":
+                d64 = days.astype(np.float64)
+                if not (np.isfinite(d64).all() and (d64 == np.floor(d64)).all()):
+                    raise ValueError("days_ago must be whole days")
+                days = d64
+            if days.size and days.min() < 0:
+                raise ValueError("days_ago must be >= 0")
+            w = w * np.exp(-time_decay * days.astype(np.float64))
+        return w
+
+    def fit_interactions(self, user_ids, item_ids, *, weights=None, days_ago=None,
+                         time_decay: float = 0.0, iterations: Optional[int] = None,
                          track_loss: bool = False):
         """Fit from (user, item) interaction arrays or tensors (duplicates allowed; ids out of
-        range raise IndexError): builds the `UserHistory`, keeps it, runs the sweeps."""
+        range raise IndexError): builds the `UserHistory`, keeps it, runs the sweeps.
+
+        `weights` (one finite value >= 0 per transaction) and/or `days_ago` (whole days >= 0)
+        with `time_decay` >= 0 make it a weighted fit: a transaction weighs
+        weights * exp(-time_decay * days_ago) (float64 on the host), a pair the sum of its
+        transactions (`UserHistory.from_interactions`).  With neither, this is the unweighted
+        fit and its bits."""
         _lib.require_gpu(self.item_embeddings.weight)
         u = user_ids.detach().cpu().numpy() if isinstance(user_ids, torch.Tensor) else user_ids
         i = item_ids.detach().cpu().numpy() if isinstance(item_ids, torch.Tensor) else item_ids
-        hist = UserHistory.from_interactions(np.asarray(u).reshape(-1), np.asarray(i).reshape(-1),
-                                             self.num_users, self.num_items, self.device)
+        u, i = np.asarray(u).reshape(-1), np.asarray(i).reshape(-1)
+        w = self._interaction_weights(u.shape[0], weights, days_ago, time_decay)
+        hist = UserHistory.from_interactions(u, i, self.num_users, self.num_items, self.device,
+                                             weights=w)
         return self.fit_history(hist, iterations=iterations, track_loss=track_loss)
 
     def _need_history(self, history: Optional[UserHistory] = None) -> UserHistory:
@@ -190,7 +257,7 @@ class ImplicitALS(MatrixFactorization):
     def loss(self) -> float:
         """L(X, Y) over the model's history in float64, without a [U, I] matrix:
         sum_{u,i} (x_u . y_i)^2 = tr((X^T X)(Y^T Y)); each history pair then trades its s^2 for
-        (1 + alpha)(1 - s)^2; plus the regulariser."""
+        (1 + alpha w)(1 - s)^2 (w = 1 without weights); plus the regulariser."""
         X, Y = self._tables()
         h = self._need_history()
         X64, Y64 = X.to(torch.float64), Y.to(torch.float64)
@@ -200,31 +267,71 @@ class ImplicitALS(MatrixFactorization):
         items = h.hist_idx[:h.nnz].to(torch.int64)
         for p0 in range(0, h.nnz, LOSS_PAIR_CHUNK):
             s = (X64[users[p0:p0 + LOSS_PAIR_CHUNK]] * Y64[items[p0:p0 + LOSS_PAIR_CHUNK]]).sum(1)
-            total = total + ((1.0 + self.alpha) * (1.0 - s) ** 2 - s ** 2).sum()
+            c = 1.0 + self.alpha
+            if h.hist_w is not None:
+                c = 1.0 + self.alpha * h.hist_w[p0:min(p0 + LOSS_PAIR_CHUNK, h.nnz)].to(torch.float64)
+            total = total + (c * (1.0 - s) ** 2 - s ** 2).sum()
         total = total + self.regularization * ((X64 ** 2).sum() + (Y64 ** 2).sum())
         return float(total)
 
     # ------------------------------------------------------------------ fold-in
-    def user_factors(self, baskets) -> torch.Tensor:
+    def _weighted_basket_csr(self, baskets, weights):
+        """(ptr, idx, n, w): `_basket_csr` plus the fp32 weights aligned with idx (None without
+        `weights`, whatever the fit was: the unweighted entry, weight 1).  For a list of baskets,
+        `weights` is a list of per-basket sequences aligned with the items, and a repeated item's
+        weights are summed by `UserHistory.from_interactions`' rule; for a (ptr, idx) CSR it is a
+        flat array aligned with idx."""
+        if weights is None:
+            return (*self._basket_csr(baskets), None)
+        dev = self.device
+        if isinstance(baskets, tuple) and len(baskets) == 2 and all(
+                isinstance(x, (torch.Tensor, np.ndarray)) for x in baskets):
+            ptr, idx, n = self._basket_csr(baskets)
+            w = torch.as_tensor(weights).reshape(-1).to(torch.float32)
+            if w.numel() != torch.as_tensor(baskets[1]).numel():
+                raise ValueError("weights must be aligned with the CSR's idx")
+            if w.numel() == 0:
+                w = torch.zeros(1, dtype=torch.float32)
+            return ptr, idx, n, w.to(dev).contiguous()
+        sets = [list(b) for b in baskets]
+        ws = [list(x) for x in weights]
+        if len(ws) != len(sets) or any(len(a) != len(b) for a, b in zip(sets, ws)):
+            raise ValueError("weights must hold one sequence per basket, aligned with its items")
+        rows = np.repeat(np.arange(len(sets), dtype=np.int64),
+                         np.asarray([len(b) for b in sets], np.int64))
+        flat = np.fromiter((int(x) for b in sets for x in b), np.int64, count=len(rows))
+        bad = (flat >= self.num_items) | (flat < -self.num_items)
+        if bad.any():
+            raise IndexError(f"index {int(flat[bad][0])} is out of bounds for dimension 1 with "
+                             f"size {self.num_items}")
+        flat = np.where(flat < 0, flat + self.num_items, flat)
+        wflat = np.fromiter((float(x) for b in ws for x in b), np.float64, count=len(rows))
+        h = UserHistory.from_interactions(rows, flat, max(len(sets), 1), self.num_items, dev,
+                                          weights=wflat)
+        return h.hist_ptr[:len(sets) + 1].contiguous(), h.hist_idx, len(sets), h.hist_w
+
+    def user_factors(self, baskets, weights=None) -> torch.Tensor:
         """[n, d] fold-in vectors of n baskets (a list of item-id iterables, or a (ptr, idx) CSR
-        with ascending unique rows): the user half-step against the fitted Y."""
+        with ascending unique rows): the user half-step against the fitted Y.  `weights`: a
+        weight per basket item ("three of these", "just viewed"), see `_weighted_basket_csr`."""
         gram = self._item_gram()
         _, Y = self._tables()
-        ptr, idx, n = self._basket_csr(baskets)
+        ptr, idx, n, w = self._weighted_basket_csr(baskets, weights)
         out = torch.empty(n, self.embedding_dim, dtype=torch.float32, device=Y.device)
-        self._solve(ptr, idx, n, Y, gram, None, n, out)
+        self._solve(ptr, idx, n, Y, gram, None, n, out, w)
         _lib.sync_check(Y.device)   # a CSR given by the caller may hold any id
         return out
 
-    def recommend_for_items(self, baskets, filter_seen: bool = True, k: Optional[int] = None):
+    def recommend_for_items(self, baskets, filter_seen: bool = True, k: Optional[int] = None, *,
+                            weights=None):
         """(scores [n, k], items [n, k]) for n baskets of item ids -- visitors without a user
-        index: the fold-in vectors are the user table of the dot-product top-K.
-        `filter_seen` removes each basket's own items from its answer."""
+        index: the fold-in vectors (`user_factors(baskets, weights)`) are the user table of the
+        dot-product top-K.  `filter_seen` removes each basket's own items from its answer."""
         k = self.top_k if k is None else k
         gram = self._item_gram()
         _, Y = self._tables()
         dev, d = Y.device, self.embedding_dim
-        ptr, idx, n = self._basket_csr(baskets)
+        ptr, idx, n, w = self._weighted_basket_csr(baskets, weights)
         kk = min(k, self.num_items)
         if kk <= 0:
             return empty_topk(k, ptr[:n])
@@ -232,7 +339,7 @@ class ImplicitALS(MatrixFactorization):
             return (torch.empty(0, kk, dtype=torch.float32, device=dev),
                     torch.empty(0, kk, dtype=torch.int64, device=dev))
         F = torch.empty(n, d, dtype=torch.float32, device=dev)
-        self._solve(ptr, idx, n, Y, gram, None, n, F)
+        self._solve(ptr, idx, n, Y, gram, None, n, F, w)
         rows = torch.arange(n, dtype=torch.int64, device=dev)
         ub = torch.zeros(n, dtype=torch.float32, device=dev)
         ib, gb = f32c(self.item_bias.weight).reshape(-1), f32c(self.global_bias)
@@ -258,13 +365,14 @@ class ImplicitALS(MatrixFactorization):
 
     def refresh_users(self, user_ids, history: Optional[UserHistory] = None):
         """Recompute the stored factors of `user_ids` from `history` (default: the model's own)
-        against the fitted Y -- a customer who bought something since the fit, without a refit."""
+        against the fitted Y -- a customer who bought something since the fit, without a refit.
+        A history with weights takes the weighted entry, as in the fit."""
         h = self._need_history(history)
         u, _ = self._ids(user_ids, self.num_users)
         gram = self._item_gram()
         X, Y = self._tables()
         out = torch.empty(u.numel(), self.embedding_dim, dtype=torch.float32, device=Y.device)
-        self._solve(h.hist_ptr, h.hist_idx, self.num_users, Y, gram, u, u.numel(), out)
+        self._solve(h.hist_ptr, h.hist_idx, self.num_users, Y, gram, u, u.numel(), out, h.hist_w)
         _lib.sync_check(Y.device)
         X[u] = out
         return self

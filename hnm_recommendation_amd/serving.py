@@ -153,12 +153,16 @@ class Recommender:
             self._history_dev = model.history
         return model
 
-    def add_als(self, user_ids, item_ids, **kw) -> ImplicitALS:
+    def add_als(self, user_ids, item_ids, weights=None, days_ago=None, time_decay: float = 0.0,
+                **kw) -> ImplicitALS:
         """Fit an `ImplicitALS` (keywords: embedding_dim, regularization, alpha, iterations,
         seed, top_k) on the transactions' (user, item) pairs and register it as "implicit_als".
+        `weights` / `days_ago` / `time_decay`: per-transaction confidence weights, as in
+        `ImplicitALS.fit_interactions` (quantities, a recency decay).
         Its history becomes the recommender's device history when the recommender has none."""
         model = ImplicitALS(self.num_users, self.num_items, **kw).to(self.device)
-        model.fit_interactions(user_ids, item_ids)
+        model.fit_interactions(user_ids, item_ids, weights=weights, days_ago=days_ago,
+                               time_decay=time_decay)
         self.add_model(ALS, model)
         if not self.user_history and self._history_dev is None:
             self._history_dev = model.history
@@ -300,19 +304,31 @@ class Recommender:
 
     def get_recommendations_for_items(self, item_ids, num_items: int = 12,
                                       model_name: str = ITEM_CF,
-                                      include_scores: bool = False) -> Dict:
+                                      include_scores: bool = False, item_weights=None) -> Dict:
         """A visitor without a user index: recommendations from a basket of item indices (the
-        basket's own items are not recommended back).  ValueError for an unknown model, a model
-        that cannot answer from items, or an item outside [0, num_items)."""
+        basket's own items are not recommended back).  `item_weights`: one finite weight >= 0
+        per entry of `item_ids` ("three of these", "just viewed"; a repeated item's weights are
+        summed), for an ImplicitALS.  ValueError for an unknown model, a model that cannot answer
+        from items, an item outside [0, num_items), or weights given to another model."""
         self._check_num_items(num_items)
         name, model = self._resolve_model(model_name)
         if not isinstance(model, (ItemCF, ImplicitALS)):
             raise ValueError(f"model {name} cannot answer from a basket of items")
-        basket = sorted({int(i) for i in item_ids})
+        if item_weights is not None and not isinstance(model, ImplicitALS):
+            raise ValueError(f"model {name} takes no item weights (only {ALS} does)")
+        given = [int(i) for i in item_ids]
+        basket = sorted(set(given))
         if basket and not 0 <= basket[0] <= basket[-1] < self.num_items:
             raise ValueError(f"item indices must be in [0, {self.num_items})")
         with torch.no_grad():
-            vals, items = model.recommend_for_items([basket], filter_seen=True, k=num_items)
+            if item_weights is not None:
+                ws = [float(x) for x in item_weights]
+                if len(ws) != len(given):
+                    raise ValueError("item_weights must have one entry per item id")
+                vals, items = model.recommend_for_items([given], filter_seen=True, k=num_items,
+                                                        weights=[ws])
+            else:
+                vals, items = model.recommend_for_items([basket], filter_seen=True, k=num_items)
         vals, items = vals.cpu().tolist(), items.cpu().tolist()
         if isinstance(model, ImplicitALS):
             # every row is full: nothing to back-fill; a basket that leaves fewer than num_items

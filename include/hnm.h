@@ -780,6 +780,33 @@ hnm_status hnm_als_solve_rows_f32(hnm_ctx* ctx, const int64_t* ptr, const int32_
                                   int64_t n_rows, const float* tab, int64_t tab_rows, int64_t ld,
                                   int64_t d, const float* gram, float alpha, float reg,
                                   const int64_t* row_ids, int64_t B, float* out, int64_t ldo);
+/* The same half-step with a confidence weight per stored entry: c_m = 1 + alpha * w_m, p = 1
+ * (Hu, Koren & Volinsky's c_ui = 1 + alpha r_ui; r = a purchase count, a recency decay, ...).
+ * w f32, aligned with idx (w[p] is the weight of entry idx[p]); every other argument is
+ * hnm_als_solve_rows_f32's.  For a row with entries j_0, j_1, ... and weights w_0, w_1, ... in
+ * stored order, in fp32:
+ *   S[i][c] = fmaf chain over m of fl(w_m * t_{j_m}[i]) * t_{j_m}[c], from 0.0f      (c <= i)
+ *   b0[c]   = ((0 + t_{j_0}[c]) + t_{j_1}[c]) + ...
+ *   bw[c]   = fmaf chain over m: acc = fmaf(w_m, t_{j_m}[c], acc), from 0.0f
+ *   A[i][c] = fmaf(alpha, S[i][c], gram[i][c]) (+ reg when i == c)
+ *   b[c]    = fmaf(alpha, bw[c], b0[c])
+ *   out     = A^-1 b   -- the Cholesky and back-substitution above, word for word
+ * (the weight scales the factor indexed by the output ROW i).  Two identities hold bit for bit
+ * whenever 1.0f + alpha' is exact in fp32 for the unweighted alpha' named: every weight 1.0f
+ * gives hnm_als_solve_rows_f32's bits at alpha' = alpha; every weight 2^e gives its bits at
+ * alpha' = 2^e * alpha.  A weight of 0 is legal: the entry then counts in b0 (and in nothing
+ * else).  A negative or non-finite weight raises its own bit of the ctx error word (HNM_EINVAL
+ * from hnm_ctx_check) and that output row is NaN; the other rows are unaffected, and an id out
+ * of range still reports HNM_EOOB (which hnm_ctx_check names first when both were seen).
+ * w == NULL with work to do: HNM_EINVAL.  Every other status, the B = 0 / n_rows = 0 rule, one
+ * workgroup per row, no floating-point atomics and "a row's bits depend on its inputs alone"
+ * are hnm_als_solve_rows_f32's. */
+hnm_status hnm_als_solve_rows_weighted_f32(hnm_ctx* ctx, const int64_t* ptr, const int32_t* idx,
+                                           const float* w, int64_t n_rows, const float* tab,
+                                           int64_t tab_rows, int64_t ld, int64_t d,
+                                           const float* gram, float alpha, float reg,
+                                           const int64_t* row_ids, int64_t B, float* out,
+                                           int64_t ldo);
 
 #ifdef __cplusplus
 }
