@@ -9,7 +9,7 @@ exposed through modules that mirror the reference's `src/models` surface.
 """
 from .evaluation import RecommendationMetrics
 from .models import (ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF, PopularityBaseline,
-                     UserHistory, WideDeep)
+                     UserHistory, WeightedItemCF, WideDeep)
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
-           "ItemCF", "ImplicitALS", "RecommendationMetrics", "UserHistory"]
+           "ItemCF", "WeightedItemCF", "ImplicitALS", "RecommendationMetrics", "UserHistory"]

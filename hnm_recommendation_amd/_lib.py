@@ -172,6 +172,13 @@ _SIGS = {
     "hnm_itemcf_topk_f32": (_i32, [_p, _p, _p, _i64, C.c_int, _p, _p, _i64, _p, _i64, _p, _p,
                                    C.c_int, _p, _p]),
     "hnm_itemcf_route": (_i32, [_p, C.c_int, _i64, C.POINTER(C.c_int)]),
+    # the three entries above with hist_w (fp32, aligned with hist_idx) after hist_idx
+    "hnm_itemcf_fit_weighted_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, C.c_int, C.c_double, _i64,
+                                           C.c_int, _p, _p, _p]),
+    "hnm_itemcf_scores_weighted_f32": (_i32, [_p, _p, _p, _i64, C.c_int, _p, _p, _p, _i64, _p,
+                                              _i64, _p, _i64]),
+    "hnm_itemcf_topk_weighted_f32": (_i32, [_p, _p, _p, _i64, C.c_int, _p, _p, _p, _i64, _p, _i64,
+                                            _p, _p, C.c_int, _p, _p]),
     # ctx, tab, rows, ld, d, out [d, d]
     "hnm_als_gram_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p]),
     # ctx, ptr, idx, n_rows, tab, tab_rows, ld, d, gram, alpha, reg, row_ids, B, out, ldo

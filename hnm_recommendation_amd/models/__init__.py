@@ -4,9 +4,9 @@ from .matrix_factorization import MatrixFactorization
 from .neural_cf import NeuralCF
 from .popularity import PopularityBaseline
 from .base import UserHistory
-from .item_cf import ItemCF
+from .item_cf import ItemCF, WeightedItemCF
 from .implicit_als import ImplicitALS
 from .wide_deep import WideDeep
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
-           "ItemCF", "ImplicitALS", "UserHistory"]
+           "ItemCF", "WeightedItemCF", "ImplicitALS", "UserHistory"]

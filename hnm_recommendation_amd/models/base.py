@@ -127,6 +127,39 @@ def _history_arrays(keys, sets, num_items: int):
     return ptr, items.astype(np.int32)
 
 
+def interaction_weights(n: int, weights, days_ago, time_decay: float):
+    """float64 [n] per-transaction weights, `weights` (default 1) times
+    exp(-time_decay * days_ago) (PopularityBaseline's convention), or None when neither
+    `weights` nor `days_ago` is given.  ValueError for a negative time_decay, fractional or
+    negative days, or a shape mismatch.  The rule of every fitted model that takes weights
+    (ImplicitALS, a weighted ItemCF)."""
+    time_decay = float(time_decay)
+    if not time_decay >= 0.0 or not np.isfinite(time_decay):
+        raise ValueError("time_decay must be finite and >= 0")
+    if weights is None and days_ago is None:
+        return None
+
+    def host(a, what):
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        a = a.reshape(-1)
+        if a.shape[0] != n:
+            raise ValueError(f"{what} must have one entry per interaction")
+        return a
+
+    w = np.ones(n, np.float64) if weights is None else host(weights, "weights").astype(np.float64)
+    if days_ago is not None:
+        days = host(days_ago, "days_ago")
+        if days.dtype.kind not in "iu":
+            d64 = days.astype(np.float64)
+            if not (np.isfinite(d64).all() and (d64 == np.floor(d64)).all()):
+                raise ValueError("days_ago must be whole days")
+            days = d64
+        if days.size and days.min() < 0:
+            raise ValueError("days_ago must be >= 0")
+        w = w * np.exp(-time_decay * days.astype(np.float64))
+    return w
+
+
 class UserHistory:
     """Device-resident per-user item history (CSR over user ids), built ONCE, for the
     -inf filter of batched recommend calls without a host round trip per batch.
@@ -157,7 +190,8 @@ class UserHistory:
         product; ValueError otherwise).  The weight of a distinct pair is the float64 sum of its
         transactions' weights, taken in ascending weight order and then rounded to fp32, so a
         permutation of the transactions gives the same bits: `hist_w`, an fp32 device tensor
-        aligned with `hist_idx` (None without `weights`).  Only ImplicitALS reads it."""
+        aligned with `hist_idx` (None without `weights`).  ImplicitALS reads it as the pair's
+        confidence, a weighted ItemCF in its fit and in a user's sums."""
         u = np.asarray(user_ids, np.int64)
         i = np.asarray(item_ids, np.int64)
         if u.shape != i.shape:

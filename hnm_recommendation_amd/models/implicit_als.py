@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .base import UserHistory, dense_topk, empty_topk, f32c
+from .base import UserHistory, dense_topk, empty_topk, f32c, interaction_weights
 from .item_cf import ItemCF
 from .matrix_factorization import MatrixFactorization
 
@@ -84,6 +84,7 @@ class ImplicitALS(MatrixFactorization):
         return out
 
     _basket_csr = ItemCF._basket_csr   # the same validation of a list of baskets / a (ptr, idx) CSR
+    _weighted_basket_csr = ItemCF._weighted_basket_csr   # and of their per-entry weights
     set_history = ItemCF.set_history
 
     # ------------------------------------------------------------------ the entries
@@ -189,37 +190,7 @@ class ImplicitALS(MatrixFactorization):
         _lib.sync_check(dev)
         return self
 
-    @staticmethod
-    def _interaction_weights(n: int, weights, days_ago, time_decay: float):
-        """float64 [n] per-transaction weights, `weights` (default 1) times
-        exp(-time_decay * days_ago) (PopularityBaseline's convention), or None when neither
-        `weights` nor `days_ago` is given.  ValueError for a negative time_decay, fractional or
-        negative days, or a shape mismatch."""
-        time_decay = float(time_decay)
-        if not time_decay >= 0.0 or not np.isfinite(time_decay):
-            raise ValueError("time_decay must be finite and >= 0")
-        if weights is None and days_ago is None:
-            return None
-
-        def host(a, what):
-            a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-            a = a.reshape(-1)
-            if a.shape[0] != n:
-                raise ValueError(f"{what} must have one entry per interaction")
-            return a
-
-        w = np.ones(n, np.float64) if weights is None else host(weights, "weights").astype(np.float64)
-        if days_ago is not None:
-            days = host(days_ago, "days_ago")
-            if days.dtype.kind not in "iu":
-                d64 = days.astype(np.float64)
-                if not (np.isfinite(d64).all() and (d64 == np.floor(d64)).all()):
-                    raise ValueError("days_ago must be whole days")
-                days = d64
-            if days.size and days.min() < 0:
-                raise ValueError("days_ago must be >= 0")
-            w = w * np.exp(-time_decay * days.astype(np.float64))
-        return w
+    _interaction_weights = staticmethod(interaction_weights)   # the old name; now in base.py
 
     def fit_interactions(self, user_ids, item_ids, *, weights=None, days_ago=None,
                          time_decay: float = 0.0, iterations: Optional[int] = None,
@@ -275,41 +246,6 @@ class ImplicitALS(MatrixFactorization):
         return float(total)
 
     # ------------------------------------------------------------------ fold-in
-    def _weighted_basket_csr(self, baskets, weights):
-        """(ptr, idx, n, w): `_basket_csr` plus the fp32 weights aligned with idx (None without
-        `weights`, whatever the fit was: the unweighted entry, weight 1).  For a list of baskets,
-        `weights` is a list of per-basket sequences aligned with the items, and a repeated item's
-        weights are summed by `UserHistory.from_interactions`' rule; for a (ptr, idx) CSR it is a
-        flat array aligned with idx."""
-        if weights is None:
-            return (*self._basket_csr(baskets), None)
-        dev = self.device
-        if isinstance(baskets, tuple) and len(baskets) == 2 and all(
-                isinstance(x, (torch.Tensor, np.ndarray)) for x in baskets):
-            ptr, idx, n = self._basket_csr(baskets)
-            w = torch.as_tensor(weights).reshape(-1).to(torch.float32)
-            if w.numel() != torch.as_tensor(baskets[1]).numel():
-                raise ValueError("weights must be aligned with the CSR's idx")
-            if w.numel() == 0:
-                w = torch.zeros(1, dtype=torch.float32)
-            return ptr, idx, n, w.to(dev).contiguous()
-        sets = [list(b) for b in baskets]
-        ws = [list(x) for x in weights]
-        if len(ws) != len(sets) or any(len(a) != len(b) for a, b in zip(sets, ws)):
-            raise ValueError("weights must hold one sequence per basket, aligned with its items")
-        rows = np.repeat(np.arange(len(sets), dtype=np.int64),
-                         np.asarray([len(b) for b in sets], np.int64))
-        flat = np.fromiter((int(x) for b in sets for x in b), np.int64, count=len(rows))
-        bad = (flat >= self.num_items) | (flat < -self.num_items)
-        if bad.any():
-            raise IndexError(f"index {int(flat[bad][0])} is out of bounds for dimension 1 with "
-                             f"size {self.num_items}")
-        flat = np.where(flat < 0, flat + self.num_items, flat)
-        wflat = np.fromiter((float(x) for b in ws for x in b), np.float64, count=len(rows))
-        h = UserHistory.from_interactions(rows, flat, max(len(sets), 1), self.num_items, dev,
-                                          weights=wflat)
-        return h.hist_ptr[:len(sets) + 1].contiguous(), h.hist_idx, len(sets), h.hist_w
-
     def user_factors(self, baskets, weights=None) -> torch.Tensor:
         """[n, d] fold-in vectors of n baskets (a list of item-id iterables, or a (ptr, idx) CSR
         with ascending unique rows): the user half-step against the fitted Y.  `weights`: a

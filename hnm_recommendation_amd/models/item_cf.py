@@ -14,6 +14,12 @@ Three HIP entries (`csrc/itemcf.hip`, contract in `include/hnm.h`):
   [B, num_items] matrix; a row is a user's history or, without user ids, a basket
   (`recommend_for_items`: a visitor without a user index).
 
+Each entry has a weighted sibling (`hnm_itemcf_*_weighted_f32`: `hist_w`, an fp32 weight per
+history entry -- a purchase count times a recency decay, `UserHistory.hist_w`).  `WeightedItemCF`
+is the `ItemCF` that uses them: the fit counts q_ui * q_uj in fixed point (integers: still the
+same bits on every run) instead of 1, a user's or basket's sum takes w_j * sim(j -> i).  A plain
+`ItemCF` never calls them and refuses weights.
+
 Top-K convention (as `PopularityBaseline`): the unmasked items with score > 0 in (score
 descending, item ascending) order, rows with fewer than k of them end in (-inf, -1).  History
 items are not excluded by themselves: the filter does that, as for every other model.
@@ -28,13 +34,16 @@ import torch
 
 from .. import _lib
 from ..evaluation import RecommendationMetrics
-from .base import RecModule, UserHistory, _history_arrays, dense_topk, empty_topk, filter_csr
+from .base import (RecModule, UserHistory, _history_arrays, dense_topk, empty_topk, filter_csr,
+                   interaction_weights)
 
 MAX_NEIGHBORS = 64   # one lane per neighbour
 FUSED_MAX_K = 64     # hnm_itemcf_topk_f32; above: dense rows + dense_topk
 
 
 class ItemCF(RecModule):
+    weighted = False     # WeightedItemCF: True (the hyperparameter "weighted" of its hparams)
+
     def __init__(self, num_users: int, num_items: int, num_neighbors: int = 64,
                  shrink: float = 0.0, max_history: int = 0, top_k: int = 12):
         super().__init__()
@@ -85,9 +94,19 @@ class ItemCF(RecModule):
         self.history = history
         return self
 
+    def _row_weights(self, history: UserHistory):
+        """The weights a history row is served with: `hist_w` for a weighted model (None when the
+        history has none: served unweighted), None for a plain one."""
+        return history.hist_w if self.weighted else None
+
     def fit_history(self, history: UserHistory, *, _window: int = 0):
         """Fit on a `UserHistory` and keep it as the model's history: one
-        `hnm_itemcf_fit_f32` call (`_window`: item columns per LDS pass, for tests)."""
+        `hnm_itemcf_fit_f32` call (`_window`: item columns per LDS pass, for tests).  A weighted
+        model needs `history.hist_w` (ValueError without) and calls
+        `hnm_itemcf_fit_weighted_f32`."""
+        if self.weighted and isinstance(history, UserHistory) and history.hist_w is None:
+            raise ValueError("a weighted ItemCF is fitted on a history with weights "
+                             "(UserHistory.from_interactions(..., weights=))")
         _lib.require_gpu(self.neighbor_idx)
         self.set_history(history)
         dev = self.device
@@ -98,23 +117,46 @@ class ItemCF(RecModule):
             t = getattr(self, name)
             if t.dtype != dtype or not t.is_contiguous():
                 setattr(self, name, t.to(dtype).contiguous())
-        _lib.check(_lib.fn("hnm_itemcf_fit_f32")(
-            _lib.ctx(dev), _lib.ptr(history.hist_ptr), _lib.ptr(history.hist_idx), self.num_users,
-            self.num_items, self.num_neighbors, self.shrink, self.max_history, int(_window),
-            _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val), _lib.ptr(self.item_count)),
-            "hnm_itemcf_fit_f32")
+        tail = (self.num_users, self.num_items, self.num_neighbors, self.shrink, self.max_history,
+                int(_window), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
+                _lib.ptr(self.item_count))
+        if self.weighted:
+            _lib.check(_lib.fn("hnm_itemcf_fit_weighted_f32")(
+                _lib.ctx(dev), _lib.ptr(history.hist_ptr), _lib.ptr(history.hist_idx),
+                _lib.ptr(history.hist_w), *tail), "hnm_itemcf_fit_weighted_f32")
+        else:
+            _lib.check(_lib.fn("hnm_itemcf_fit_f32")(
+                _lib.ctx(dev), _lib.ptr(history.hist_ptr), _lib.ptr(history.hist_idx), *tail),
+                "hnm_itemcf_fit_f32")
         _lib.sync_check(dev)
         self._is_fitted = True
         return self
 
-    def fit_interactions(self, user_ids, item_ids, *, _window: int = 0):
+    def fit_interactions(self, user_ids, item_ids, *, weights=None, days_ago=None,
+                         time_decay: float = 0.0, _window: int = 0):
         """Fit from (user, item) interaction arrays or tensors (duplicates allowed; ids out of
-        range raise IndexError): builds the `UserHistory`, keeps it, runs the fit."""
-        _lib.require_gpu(self.neighbor_idx)
+        range raise IndexError): builds the `UserHistory`, keeps it, runs the fit.
+
+        A weighted model takes `weights` (one finite value >= 0 per transaction) and / or
+        `days_ago` (whole days >= 0) with `time_decay` >= 0, by `ImplicitALS.fit_interactions`'
+        rules: a transaction weighs weights * exp(-time_decay * days_ago), a pair the sum of its
+        transactions; with neither a transaction weighs 1, a pair its number of purchases (pairs
+        that occur once each give the unweighted table's bits).  A plain model raises ValueError
+        for either."""
+        if not self.weighted and (weights is not None or days_ago is not None):
+            raise ValueError("this ItemCF is not weighted: build a WeightedItemCF to fit with "
+                             "weights or days_ago")
+        if not self.weighted:   # a weighted model validates its arguments first (fit_history asks)
+            _lib.require_gpu(self.neighbor_idx)
         u = user_ids.detach().cpu().numpy() if isinstance(user_ids, torch.Tensor) else user_ids
         i = item_ids.detach().cpu().numpy() if isinstance(item_ids, torch.Tensor) else item_ids
-        hist = UserHistory.from_interactions(np.asarray(u).reshape(-1), np.asarray(i).reshape(-1),
-                                             self.num_users, self.num_items, self.device)
+        u, i = np.asarray(u).reshape(-1), np.asarray(i).reshape(-1)
+        w = None
+        if self.weighted:
+            w = interaction_weights(u.shape[0], weights, days_ago, time_decay)
+            w = np.ones(u.shape[0], np.float64) if w is None else w
+        hist = UserHistory.from_interactions(u, i, self.num_users, self.num_items, self.device,
+                                             weights=w)
         return self.fit_history(hist, _window=_window)
 
     # ------------------------------------------------------------------ answering
@@ -139,31 +181,43 @@ class ItemCF(RecModule):
             raise ValueError(f"history lives on {self.history.device}, the model on {self.device}")
         return self.history
 
-    def _dense(self, hptr, hidx, rows: int, u: Optional[torch.Tensor], B: int) -> torch.Tensor:
+    def _dense(self, hptr, hidx, rows: int, u: Optional[torch.Tensor], B: int,
+               w: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[B, num_items] scores; `w` (fp32, aligned with hidx) selects the weighted entry."""
         out = torch.empty(B, self.num_items, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.fn("hnm_itemcf_scores_f32")(
-            _lib.ctx(self.device), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
-            self.num_items, self.num_neighbors, _lib.ptr(hptr), _lib.ptr(hidx), rows, _lib.ptr(u),
-            B, _lib.ptr(out), out.stride(0) if B else self.num_items), "hnm_itemcf_scores_f32")
+        head = (_lib.ctx(self.device), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
+                self.num_items, self.num_neighbors, _lib.ptr(hptr), _lib.ptr(hidx))
+        tail = (rows, _lib.ptr(u), B, _lib.ptr(out), out.stride(0) if B else self.num_items)
+        if w is None:
+            _lib.check(_lib.fn("hnm_itemcf_scores_f32")(*head, *tail), "hnm_itemcf_scores_f32")
+        else:
+            _lib.check(_lib.fn("hnm_itemcf_scores_weighted_f32")(*head, _lib.ptr(w), *tail),
+                       "hnm_itemcf_scores_weighted_f32")
         return out
 
-    def _topk(self, hptr, hidx, rows: int, u: Optional[torch.Tensor], B: int, mptr, midx, k: int):
-        """(scores [B, k], items [B, k]) of B history rows (u None: the CSR's own rows)."""
+    def _topk(self, hptr, hidx, rows: int, u: Optional[torch.Tensor], B: int, mptr, midx, k: int,
+              w: Optional[torch.Tensor] = None):
+        """(scores [B, k], items [B, k]) of B history rows (u None: the CSR's own rows); `w`
+        (fp32, aligned with hidx) selects the weighted entries."""
         dev = self.device
         if k <= FUSED_MAX_K:
             out_v = torch.empty(B, k, dtype=torch.float32, device=dev)
             out_i = torch.empty(B, k, dtype=torch.int64, device=dev)
-            _lib.check(_lib.fn("hnm_itemcf_topk_f32")(
-                _lib.ctx(dev), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
-                self.num_items, self.num_neighbors, _lib.ptr(hptr), _lib.ptr(hidx), rows,
-                _lib.ptr(u), B, _lib.ptr(mptr), _lib.ptr(midx), k, _lib.ptr(out_v),
-                _lib.ptr(out_i)), "hnm_itemcf_topk_f32")
+            head = (_lib.ctx(dev), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
+                    self.num_items, self.num_neighbors, _lib.ptr(hptr), _lib.ptr(hidx))
+            tail = (rows, _lib.ptr(u), B, _lib.ptr(mptr), _lib.ptr(midx), k, _lib.ptr(out_v),
+                    _lib.ptr(out_i))
+            if w is None:
+                _lib.check(_lib.fn("hnm_itemcf_topk_f32")(*head, *tail), "hnm_itemcf_topk_f32")
+            else:
+                _lib.check(_lib.fn("hnm_itemcf_topk_weighted_f32")(*head, _lib.ptr(w), *tail),
+                           "hnm_itemcf_topk_weighted_f32")
             return out_v, out_i
         # k > 64: the dense rows and the row top-k kernel; slots without a positive score
         # (zero scores, masked items) become (-inf, -1)
         if B == 0:
             return empty_rows(B, k, dev)
-        out_v, out_i = dense_topk(self._dense(hptr, hidx, rows, u, B), k, mptr, midx)
+        out_v, out_i = dense_topk(self._dense(hptr, hidx, rows, u, B, w), k, mptr, midx)
         pad = ~(out_v > 0)
         return out_v.masked_fill(pad, float("-inf")), out_i.masked_fill(pad, -1)
 
@@ -172,7 +226,8 @@ class ItemCF(RecModule):
         self._fitted()
         u, host = self._users(user_ids)
         h = self._need_history()
-        out = self._dense(h.hist_ptr, h.hist_idx, h.num_users, u, u.numel())
+        out = self._dense(h.hist_ptr, h.hist_idx, h.num_users, u, u.numel(),
+                          self._row_weights(h))
         self._check(self.device, host)
         return out
 
@@ -188,7 +243,8 @@ class ItemCF(RecModule):
         kk = min(k, self.num_items)
         if kk <= 0:
             return empty_topk(k, u)
-        out = self._topk(h.hist_ptr, h.hist_idx, h.num_users, u, u.numel(), mptr, midx, kk)
+        out = self._topk(h.hist_ptr, h.hist_idx, h.num_users, u, u.numel(), mptr, midx, kk,
+                         self._row_weights(h))
         self._check(self.device, host)
         return out
 
@@ -229,18 +285,58 @@ class ItemCF(RecModule):
             idx = torch.zeros(1, dtype=torch.int32)
         return ptr.to(dev).contiguous(), idx.to(dev).contiguous(), ptr.numel() - 1
 
-    def recommend_for_items(self, baskets, filter_seen: bool = True, k: Optional[int] = None):
+    def _weighted_basket_csr(self, baskets, weights):
+        """(ptr, idx, n, w): `_basket_csr` plus the fp32 weights aligned with idx (None without
+        `weights`, whatever the fit was: the unweighted entry, weight 1).  For a list of baskets,
+        `weights` is a list of per-basket sequences aligned with the items, and a repeated item's
+        weights are summed by `UserHistory.from_interactions`' rule; for a (ptr, idx) CSR it is a
+        flat array aligned with idx."""
+        if weights is None:
+            return (*self._basket_csr(baskets), None)
+        dev = self.device
+        if isinstance(baskets, tuple) and len(baskets) == 2 and all(
+                isinstance(x, (torch.Tensor, np.ndarray)) for x in baskets):
+            ptr, idx, n = self._basket_csr(baskets)
+            w = torch.as_tensor(weights).reshape(-1).to(torch.float32)
+            if w.numel() != torch.as_tensor(baskets[1]).numel():
+                raise ValueError("weights must be aligned with the CSR's idx")
+            if w.numel() == 0:
+                w = torch.zeros(1, dtype=torch.float32)
+            return ptr, idx, n, w.to(dev).contiguous()
+        sets = [list(b) for b in baskets]
+        ws = [list(x) for x in weights]
+        if len(ws) != len(sets) or any(len(a) != len(b) for a, b in zip(sets, ws)):
+            raise ValueError("weights must hold one sequence per basket, aligned with its items")
+        rows = np.repeat(np.arange(len(sets), dtype=np.int64),
+                         np.asarray([len(b) for b in sets], np.int64))
+        flat = np.fromiter((int(x) for b in sets for x in b), np.int64, count=len(rows))
+        bad = (flat >= self.num_items) | (flat < -self.num_items)
+        if bad.any():
+            raise IndexError(f"index {int(flat[bad][0])} is out of bounds for dimension 1 with "
+                             f"size {self.num_items}")
+        flat = np.where(flat < 0, flat + self.num_items, flat)
+        wflat = np.fromiter((float(x) for b in ws for x in b), np.float64, count=len(rows))
+        h = UserHistory.from_interactions(rows, flat, max(len(sets), 1), self.num_items, dev,
+                                          weights=wflat)
+        return h.hist_ptr[:len(sets) + 1].contiguous(), h.hist_idx, len(sets), h.hist_w
+
+    def recommend_for_items(self, baskets, filter_seen: bool = True, k: Optional[int] = None, *,
+                            weights=None):
         """(scores [n, k], items [n, k]) for n baskets of item ids -- visitors without a user
-        index.  `filter_seen` removes each basket's own items from its answer."""
+        index.  `filter_seen` removes each basket's own items from its answer.  `weights` (a
+        weighted model only, else ValueError): a weight per basket entry, a repeated item's
+        summed, see `_weighted_basket_csr`."""
+        if weights is not None and not self.weighted:
+            raise ValueError("this ItemCF is not weighted: it takes no basket weights")
         self._fitted()
         _lib.require_gpu(self.neighbor_idx)
         k = self.top_k if k is None else k
-        ptr, idx, n = self._basket_csr(baskets)
+        ptr, idx, n, w = self._weighted_basket_csr(baskets, weights)
         kk = min(k, self.num_items)
         if kk <= 0:
             return empty_topk(k, ptr[:n])
         mptr, midx = (ptr, idx) if filter_seen else (None, None)
-        out = self._topk(ptr, idx, n, None, n, mptr, midx, kk)
+        out = self._topk(ptr, idx, n, None, n, mptr, midx, kk, w)
         _lib.sync_check(self.device)   # a CSR given by the caller may hold any id
         return out
 
@@ -275,3 +371,22 @@ class ItemCF(RecModule):
 def empty_rows(B: int, k: int, device):
     return (torch.empty(B, k, dtype=torch.float32, device=device),
             torch.empty(B, k, dtype=torch.int64, device=device))
+
+
+class WeightedItemCF(ItemCF):
+    """`ItemCF` with the hyperparameter `weighted` = True (`hparams["weighted"]`; the buffers and
+    state_dict keys are ItemCF's): fitted on `UserHistory.hist_w` by
+    `hnm_itemcf_fit_weighted_f32`, a user's row weighted by the history's `hist_w`, baskets by
+    the call's `weights`.  `ItemCF.__init__` keeps its parameter list, so the flag is the class;
+    a checkpoint whose hyper-parameters hold `weighted: True` is built as this class
+    (`serving.create_model_from_checkpoint`)."""
+    weighted = True
+
+    def __init__(self, num_users: int, num_items: int, num_neighbors: int = 64,
+                 shrink: float = 0.0, max_history: int = 0, top_k: int = 12,
+                 weighted: bool = True):
+        if not weighted:
+            raise ValueError("a WeightedItemCF is weighted: build an ItemCF instead")
+        super().__init__(num_users, num_items, num_neighbors=num_neighbors, shrink=shrink,
+                         max_history=max_history, top_k=top_k)
+        self.hparams["weighted"] = True

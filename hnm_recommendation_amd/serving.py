@@ -40,7 +40,7 @@ from typing import Dict, List, Optional, Sequence, Union
 import torch
 
 from .models import (ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
-                     PopularityBaseline, WideDeep)
+                     PopularityBaseline, WeightedItemCF, WideDeep)
 from .models.base import UserHistory
 
 logger = logging.getLogger(__name__)
@@ -76,6 +76,8 @@ def create_model_from_checkpoint(model_name: str, checkpoint: Dict, num_users: i
         cls = next((c for key, c in _DISPATCH if key in model_name), None)
         if cls is None:
             return None
+        if cls is ItemCF and hparams.pop("weighted", False):   # the hyperparameter names the class
+            cls = WeightedItemCF
         model = cls(**hparams)
         if cls is LightGCN:
             if graph is None:
@@ -142,12 +144,21 @@ class Recommender:
         self.add_model(BASELINE, model)
         return model
 
-    def add_item_cf(self, user_ids, item_ids, **kw) -> ItemCF:
+    def add_item_cf(self, user_ids, item_ids, weights=None, days_ago=None,
+                    time_decay: float = 0.0, **kw) -> ItemCF:
         """Fit an `ItemCF` (keywords: num_neighbors, shrink, max_history, top_k) on the
-        transactions' (user, item) pairs and register it as "item_cf".  Its history becomes the
-        recommender's device history when the recommender has none."""
-        model = ItemCF(self.num_users, self.num_items, **kw).to(self.device)
-        model.fit_interactions(user_ids, item_ids)
+        transactions' (user, item) pairs and register it as "item_cf".  With `weights`,
+        `days_ago` or a `time_decay` > 0 it is a `WeightedItemCF` fitted on per-transaction
+        weights by `add_als`' rules (quantities, a recency decay); with none of them the plain
+        model and its bits.  Its history becomes the recommender's device history when the
+        recommender has none."""
+        if weights is not None or days_ago is not None or float(time_decay) != 0.0:
+            model = WeightedItemCF(self.num_users, self.num_items, **kw).to(self.device)
+            model.fit_interactions(user_ids, item_ids, weights=weights, days_ago=days_ago,
+                                   time_decay=time_decay)
+        else:
+            model = ItemCF(self.num_users, self.num_items, **kw).to(self.device)
+            model.fit_interactions(user_ids, item_ids)
         self.add_model(ITEM_CF, model)
         if not self.user_history and self._history_dev is None:
             self._history_dev = model.history
@@ -308,14 +319,17 @@ class Recommender:
         """A visitor without a user index: recommendations from a basket of item indices (the
         basket's own items are not recommended back).  `item_weights`: one finite weight >= 0
         per entry of `item_ids` ("three of these", "just viewed"; a repeated item's weights are
-        summed), for an ImplicitALS.  ValueError for an unknown model, a model that cannot answer
-        from items, an item outside [0, num_items), or weights given to another model."""
+        summed), for an ImplicitALS or a weighted ItemCF.  ValueError for an unknown model, a
+        model that cannot answer from items, an item outside [0, num_items), or weights given to
+        another model."""
         self._check_num_items(num_items)
         name, model = self._resolve_model(model_name)
         if not isinstance(model, (ItemCF, ImplicitALS)):
             raise ValueError(f"model {name} cannot answer from a basket of items")
-        if item_weights is not None and not isinstance(model, ImplicitALS):
-            raise ValueError(f"model {name} takes no item weights (only {ALS} does)")
+        if item_weights is not None and not (isinstance(model, ImplicitALS)
+                                             or getattr(model, "weighted", False)):
+            raise ValueError(f"model {name} takes no item weights (only {ALS} and a weighted "
+                             f"{ITEM_CF} do)")
         given = [int(i) for i in item_ids]
         basket = sorted(set(given))
         if basket and not 0 <= basket[0] <= basket[-1] < self.num_items:

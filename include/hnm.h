@@ -742,6 +742,56 @@ hnm_status hnm_itemcf_topk_f32(hnm_ctx* ctx, const int32_t* nbr_idx, const float
 /* *route = 0: a row of history_len items takes the fused LDS route of hnm_itemcf_topk_f32 with
  * N neighbours per item; 1: the dense route.  No launch, no sync. */
 hnm_status hnm_itemcf_route(hnm_ctx* ctx, int N, int64_t history_len, int* route);
+/* The weighted siblings: hist_w f32, aligned with hist_idx (hist_w[p] is the weight of entry
+ * hist_idx[p]: a purchase count, a recency decay, their product -- UserHistory.hist_w), finite
+ * and >= 0; every other argument, status and rule is the unweighted entry's, and hist_w == NULL
+ * IS the unweighted entry, bit for bit.  hnm_itemcf_route serves both.
+ *
+ * Fit.  The counts stay integers by counting in fixed point.  max_history counts entries, not
+ * weights.  With w_max = the largest weight among the kept users' entries,
+ *   s = 32768.0 / (double)w_max            q = (uint32) rint((double)w * s)      (ties to even)
+ * in float64, so w_max maps to exactly 2^15.  Over the kept users, in uint64,
+ *   n_w[i] = sum_u q_ui^2                  C_w[i, j] = sum_u q_ui * q_uj   (i != j)
+ * (a product <= 2^30, fewer than 2^31 users: < 2^61, nothing overflows; integer sums are
+ * order-free, so a run gives the same bits every time), and for C_w[i, j] > 0
+ *   sim[i, j] = (float)( (double)C_w / ( sqrt((double)n_i * (double)n_j) + (shrink * s) * s ) )
+ * one rounding per operation, no fma: shrink is in the caller's weight units squared, and with
+ * unit weights it is the unweighted shrink.  Selection, order and padding are
+ * hnm_itemcf_fit_f32's.  Entries with q == 0 are left out: item_count[i] = kept users holding i
+ * with q > 0.  w_max == 0 (or no kept entry) behaves as an empty history: every row padded,
+ * item_count zero.  A negative or non-finite weight raises its own bit of the ctx error word
+ * (HNM_EINVAL from hnm_ctx_check; HNM_EOOB is named first when both were seen) and counts as 0.
+ * Two identities hold bit for bit: every weight 1.0f gives hnm_itemcf_fit_f32's nbr_idx,
+ * nbr_val and item_count for any shrink and max_history (a power-of-two scale commutes with
+ * every rounding); every weight equal to any one constant does at shrink = 0.  `window`: uint64
+ * counters per LDS pass (0 = default 16,384 = 128 KiB of LDS, one workgroup a CU; else a multiple
+ * of 64 in [64, 16384]; up to 8,192 = 64 KiB two workgroups share a CU).  Workspace: the unweighted fit's plus 8 bytes per history entry
+ * and 8 per item. */
+hnm_status hnm_itemcf_fit_weighted_f32(hnm_ctx* ctx, const int64_t* hist_ptr,
+                                       const int32_t* hist_idx, const float* hist_w,
+                                       int64_t num_users, int64_t num_items, int N, double shrink,
+                                       int64_t max_history, int window, int32_t* nbr_idx,
+                                       float* nbr_val, int64_t* item_count);
+/* Scores.  out[b, i] = the fp32 sum over the row's items j in ascending order of
+ * fl(w_j * nbr_val(j -> i)): the product is rounded to fp32 first, then a plain add (no fma);
+ * w_j is the row's raw fp32 weight, not the quantised one.  A weight of 0 contributes nothing.  A
+ * negative or non-finite weight raises the weight bit of the error word and counts as 0. */
+hnm_status hnm_itemcf_scores_weighted_f32(hnm_ctx* ctx, const int32_t* nbr_idx,
+                                          const float* nbr_val, int64_t num_items, int N,
+                                          const int64_t* hist_ptr, const int32_t* hist_idx,
+                                          const float* hist_w, int64_t num_users,
+                                          const int64_t* user_ids, int64_t B, float* out,
+                                          int64_t ld);
+/* Fused top-K of the weighted scores: score > 0, the mask, the (score descending, item
+ * ascending) order, the (-inf, -1) padding and the h_b * N <= 4,096 route rule are
+ * hnm_itemcf_topk_f32's; both routes give the same bits. */
+hnm_status hnm_itemcf_topk_weighted_f32(hnm_ctx* ctx, const int32_t* nbr_idx,
+                                        const float* nbr_val, int64_t num_items, int N,
+                                        const int64_t* hist_ptr, const int32_t* hist_idx,
+                                        const float* hist_w, int64_t num_users,
+                                        const int64_t* user_ids, int64_t B,
+                                        const int64_t* mask_ptr, const int32_t* mask_idx, int k,
+                                        float* out_val, int64_t* out_idx);
 
 /* ---- ImplicitALS: alternating least squares for implicit feedback (Hu, Koren & Volinsky
  * 2008; no reference counterpart) ----------------------------------------------------------

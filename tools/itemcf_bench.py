@@ -15,11 +15,19 @@ At the H&M shape (U = 1,371,980, I = 105,542, E = 31,788,324 synthetic interacti
 (c) the same call as baskets with 64 of the 4,096 rows replaced by 2,000-item bulk buyers (the
     dense route): the synthetic generator draws users uniformly, so (b) holds no such row.
 
+(d) the weighted siblings (pair weights count * exp(-0.01 days)) on the same CSR:
+    hnm_itemcf_fit_weighted_f32 at windows of 4,096 / 8,192 (64 KiB of 64-bit counters, two
+    workgroups a CU) / 16,384 (128 KiB, one) against hnm_itemcf_fit_f32, and the weighted per-user
+    top-12 against the unweighted one.  Checked before timing: the weighted fit gives the same
+    bits twice and at every window, and unit weights give the unweighted table.
+    `--weighted-only` runs (d) alone (default --out then: profiles/witemcf_bench.txt).
+
 Each side is warmed up, then timed in interleaved rounds (order alternating) of at least
 `--steps` calls (and ~50 ms) between device synchronisations; medians and the spread of the
 per-round means are reported.
 """
 import argparse
+import copy
 import os
 import statistics
 import sys
@@ -30,18 +38,22 @@ import torch
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
-from hnm_recommendation_amd import ItemCF, UserHistory, _lib  # noqa: E402
+from hnm_recommendation_amd import ItemCF, UserHistory, WeightedItemCF, _lib  # noqa: E402
 from hnm_recommendation_amd import synthetic as syn  # noqa: E402
 from hnm_recommendation_amd.models.base import dense_topk  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--out", default=os.path.join(R, "profiles", "itemcf_bench.txt"))
+ap.add_argument("--out", default=None)
+ap.add_argument("--weighted-only", action="store_true")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--fit-steps", type=int, default=2)
 ap.add_argument("--rows", type=int, default=syn.HM_INTERACTIONS)
 ap.add_argument("--cpu-budget", type=float, default=60.0)
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(R, "profiles",
+                            "witemcf_bench.txt" if args.weighted_only else "itemcf_bench.txt")
 
 if not torch.cuda.is_available():
     raise SystemExit("itemcf_bench needs an AMD GPU: there is no CPU path")
@@ -98,6 +110,77 @@ hist = UserHistory.from_interactions(users_np, items_np, U, I, dev)
 lens = (hist.hist_ptr[1:] - hist.hist_ptr[:-1])
 say(f"data: U = {U}, I = {I}, E = {args.rows} drawn, {hist.nnz} distinct (user, item) pairs, "
     f"history mean {hist.nnz / U:.1f}, max {int(lens.max())}")
+
+
+
+def write_out():
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def same_table(m, idx, val, cnt):
+    return (torch.equal(m.neighbor_idx, idx) and torch.equal(m.item_count, cnt)
+            and torch.equal(m.neighbor_val.view(torch.int32), val.view(torch.int32)))
+
+
+# ------------------------------------------------------------------ (d) weighted
+def weighted_section():
+    g = torch.Generator(device="cpu").manual_seed(5)
+    n_w = hist.hist_idx.numel()
+    w = (torch.randint(1, 9, (n_w,), generator=g).to(torch.float64)
+         * torch.exp(-0.01 * torch.randint(0, 366, (n_w,), generator=g).to(torch.float64)))
+    whist = copy.copy(hist)                                # the same CSR, with weights
+    whist.hist_w = w.to(torch.float32).to(dev)
+    ones = copy.copy(hist)
+    ones.hist_w = torch.ones(n_w, dtype=torch.float32, device=dev)
+    say(f"(d) weighted: pair weights count * exp(-0.01 days): min "
+        f"{float(whist.hist_w[:hist.nnz].min()):.4f}, mean "
+        f"{float(whist.hist_w[:hist.nnz].mean()):.4f}, max "
+        f"{float(whist.hist_w[:hist.nnz].max()):.4f}")
+    plain = ItemCF(U, I, num_neighbors=N).to(dev).fit_history(hist)
+    wm = WeightedItemCF(U, I, num_neighbors=N).to(dev).fit_history(ones)
+    assert same_table(wm, plain.neighbor_idx, plain.neighbor_val, plain.item_count)
+    wm.fit_history(whist)
+    ref = (wm.neighbor_idx.clone(), wm.neighbor_val.clone(), wm.item_count.clone())
+    assert not torch.equal(ref[0], plain.neighbor_idx)
+    sides = {"hnm_itemcf_fit_f32 (unweighted, window 16384)": lambda: plain.fit_history(hist)}
+    for W in (4096, 8192, 16384):
+        sides[f"hnm_itemcf_fit_weighted_f32, window {W}"] = \
+            (lambda W=W: wm.fit_history(whist, _window=W))
+    for name, f in list(sides.items())[1:] * 2:                   # every window, twice
+        f()
+        assert same_table(wm, *ref), name
+    say(f"    fit: N = {N}; unit weights give the unweighted table's bits; the weighted fit gives "
+        "equal bits twice and at the three windows")
+    base = "hnm_itemcf_fit_f32 (unweighted, window 16384)"
+    report("", interleaved(sides, args.fit_steps, args.rounds, warm=1), base)
+    wm.fit_history(whist)
+    ub = torch.from_numpy(syn.user_batch(U, B, seed=100)).to(dev)
+    a = wm.recommend_with_scores(ub, filter_items=whist, k=K)
+    b = wm.recommend_with_scores(ub, filter_items=whist, k=K)
+    assert torch.equal(a[1], b[1]) and torch.equal(a[0].view(torch.int32), b[0].view(torch.int32))
+    wm_ones = WeightedItemCF(U, I, num_neighbors=N).to(dev)
+    wm_ones.load_state_dict(plain.state_dict())
+    wm_ones.set_history(ones)
+    a = wm_ones.recommend_with_scores(ub, filter_items=hist, k=K)
+    b = plain.recommend_with_scores(ub, filter_items=hist, k=K)
+    assert torch.equal(a[1], b[1]) and torch.equal(a[0].view(torch.int32), b[0].view(torch.int32))
+    _lib.sync_check(dev)
+    say(f"    recommend_with_scores: B = {B}, K = {K}, history filter; the weighted call gives "
+        "equal bits twice, and the unweighted call's with unit weights")
+    base = "hnm_itemcf_topk_f32 (unweighted)"
+    report("", interleaved(
+        {base: lambda: plain.recommend_with_scores(ub, filter_items=hist, k=K),
+         "hnm_itemcf_topk_weighted_f32": lambda: wm.recommend_with_scores(ub, filter_items=whist,
+                                                                          k=K)},
+        args.steps, args.rounds), base)
+
+
+if args.weighted_only:
+    weighted_section()
+    write_out()
+    sys.exit(0)
 
 # ------------------------------------------------------------------ (a) fit
 model = ItemCF(U, I, num_neighbors=N).to(dev)
@@ -248,6 +331,5 @@ report("", interleaved({"baskets = the users' histories": lambda: model.recommen
                         "64 of them 2,000-item baskets": lambda: model.recommend_for_items(bulk_csr, k=K)},
                        args.steps, args.rounds), "baskets = the users' histories")
 
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    f.write("\n".join(lines) + "\n")
+weighted_section()
+write_out()
