@@ -241,11 +241,28 @@ def check(status: int, what: str = ""):
     raise RuntimeError(f"{what}: {msg} (status {status})")
 
 
+def call(name: str, *args):
+    """One library call: raises what `check` makes of its status."""
+    check(fn(name)(*args), name)
+
+
+def call_weighted(name: str, at: int, w, *args):
+    """`call(name, *args)` for `w` None; with a weight tensor `w` the entry's weighted sibling:
+    the same signature plus one pointer, `w`'s, as argument `at` (right after the CSR's idx),
+    named `..._weighted_f32`."""
+    if w is not None:
+        name, args = name.replace("_f32", "_weighted_f32"), (*args[:at], ptr(w), *args[at:])
+    check(fn(name)(*args), name)
+
+
 def require_gpu(*tensors):
+    """RuntimeError unless every tensor (or torch.device) given is a GPU one."""
     for t in tensors:
         if t is None:
             continue
-        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        on_gpu = t.type == "cuda" if isinstance(t, torch.device) else (
+            isinstance(t, torch.Tensor) and t.is_cuda)
+        if not on_gpu:
             raise RuntimeError(
                 "hnm_recommendation_amd runs on an AMD Instinct GPU (MI355X) through its HIP "
                 "library; move the module and its inputs to a GPU device (model.to('cuda')). "

@@ -1,6 +1,6 @@
 // ItemCF: item-based collaborative filtering over the de-duplicated user -> item CSR
 // (UserHistory.hist_ptr / hist_idx: rows ascending and unique).  No reference counterpart: the
-// contract is stated in include/hnm.h and restated in numpy by tests/test_gpu_itemcf.py.
+// contract is stated in include/hnm.h and restated in numpy by tests/itemcf_oracle.py.
 //
 // Fit.  Users with more than max_history items are dropped.  Over the kept users
 //   n[i]     = users holding i                         (int32 atomics -> item_count int64)
@@ -34,7 +34,7 @@
 // Entries with q = 0 stay out of the transpose.  Serving multiplies val(j -> i) by the row's raw
 // weight w_j (one fp32 rounding) before the same plain add.  The unweighted kernels are the
 // WT = false instantiations: no extra loads, registers or LDS.  The numpy restatement of this
-// paragraph is tests/test_gpu_witemcf.py.
+// paragraph is tests/itemcf_oracle.py too.
 #include "hnm_device.h"
 #include "hnm_internal.h"
 

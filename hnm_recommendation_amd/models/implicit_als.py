@@ -35,8 +35,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .base import UserHistory, dense_topk, empty_topk, f32c, interaction_weights
-from .item_cf import ItemCF
+from .base import (HistoryModel, UserHistory, basket_csr, dense_topk, empty_rows, empty_topk, f32c,
+                   interaction_weights, interactions_history)
 from .matrix_factorization import MatrixFactorization
 
 LOSS_PAIR_CHUNK = 1 << 20   # history pairs per float64 pass of loss()
@@ -46,7 +46,9 @@ def supported_dim(d: int) -> bool:
     return 16 <= d <= 128 and d % 16 == 0
 
 
-class ImplicitALS(MatrixFactorization):
+class ImplicitALS(HistoryModel, MatrixFactorization):
+    answers_baskets = takes_basket_weights = True   # by fold-in; its rows are full
+
     def __init__(self, num_users: int, num_items: int, embedding_dim: int = 64,
                  regularization: float = 0.01, alpha: float = 40.0, iterations: int = 15,
                  seed: int = 0, top_k: int = 12):
@@ -63,7 +65,6 @@ class ImplicitALS(MatrixFactorization):
         self.save_hyperparameters()
         self.regularization, self.alpha = float(regularization), float(alpha)
         self.iterations, self.seed = int(iterations), int(seed)
-        self.history: Optional[UserHistory] = None
         self.loss_history: List[float] = []
         self._gram: Optional[torch.Tensor] = None   # Y^T Y of the fitted item table (fold-in)
         with torch.no_grad():
@@ -83,10 +84,6 @@ class ImplicitALS(MatrixFactorization):
         self._gram = None
         return out
 
-    _basket_csr = ItemCF._basket_csr   # the same validation of a list of baskets / a (ptr, idx) CSR
-    _weighted_basket_csr = ItemCF._weighted_basket_csr   # and of their per-entry weights
-    set_history = ItemCF.set_history
-
     # ------------------------------------------------------------------ the entries
     def _tables(self):
         """(X, Y): the embedding tables themselves as fp32 contiguous device tensors."""
@@ -102,26 +99,17 @@ class ImplicitALS(MatrixFactorization):
         d = self.embedding_dim
         if out is None:
             out = torch.empty(d, d, dtype=torch.float32, device=tab.device)
-        _lib.check(_lib.fn("hnm_als_gram_f32")(_lib.ctx(tab.device), _lib.ptr(tab), tab.shape[0],
-                                               tab.stride(0), d, _lib.ptr(out)),
-                   "hnm_als_gram_f32")
+        _lib.call("hnm_als_gram_f32", _lib.ctx(tab.device), _lib.ptr(tab), tab.shape[0],
+                  tab.stride(0), d, _lib.ptr(out))
         return out
 
     def _solve(self, ptr, idx, n_rows: int, tab, gram, row_ids, B: int, out, w=None):
         """One half-step; `w` (fp32, aligned with idx) selects the weighted entry."""
-        ldo = out.stride(0) if B else self.embedding_dim
-        if w is None:
-            _lib.check(_lib.fn("hnm_als_solve_rows_f32")(
-                _lib.ctx(tab.device), _lib.ptr(ptr), _lib.ptr(idx), n_rows, _lib.ptr(tab),
-                tab.shape[0], tab.stride(0), self.embedding_dim, _lib.ptr(gram), self.alpha,
-                self.regularization, _lib.ptr(row_ids), B, _lib.ptr(out), ldo),
-                "hnm_als_solve_rows_f32")
-        else:
-            _lib.check(_lib.fn("hnm_als_solve_rows_weighted_f32")(
-                _lib.ctx(tab.device), _lib.ptr(ptr), _lib.ptr(idx), _lib.ptr(w), n_rows,
-                _lib.ptr(tab), tab.shape[0], tab.stride(0), self.embedding_dim, _lib.ptr(gram),
-                self.alpha, self.regularization, _lib.ptr(row_ids), B, _lib.ptr(out), ldo),
-                "hnm_als_solve_rows_weighted_f32")
+        _lib.call_weighted(
+            "hnm_als_solve_rows_f32", 3, w, _lib.ctx(tab.device), _lib.ptr(ptr), _lib.ptr(idx),
+            n_rows, _lib.ptr(tab), tab.shape[0], tab.stride(0), self.embedding_dim, _lib.ptr(gram),
+            self.alpha, self.regularization, _lib.ptr(row_ids), B, _lib.ptr(out),
+            out.stride(0) if B else self.embedding_dim)
         return out
 
     def _item_gram(self) -> torch.Tensor:
@@ -164,11 +152,9 @@ class ImplicitALS(MatrixFactorization):
         iters = self.iterations if iterations is None else int(iterations)
         if iters < 0:
             raise ValueError("iterations must be >= 0")
-        self.set_history(history)
+        history = self.set_history(history)._need_history()
         X, Y = self._tables()
         dev = X.device
-        if history.device != dev:
-            raise ValueError(f"history lives on {history.device}, the model on {dev}")
         with torch.no_grad():
             self._init_items()
             X.zero_()
@@ -190,7 +176,7 @@ class ImplicitALS(MatrixFactorization):
         _lib.sync_check(dev)
         return self
 
-    _interaction_weights = staticmethod(interaction_weights)   # the old name; now in base.py
+    _interaction_weights = staticmethod(interaction_weights)   # the old name; now in history.py
 
     def fit_interactions(self, user_ids, item_ids, *, weights=None, days_ago=None,
                          time_decay: float = 0.0, iterations: Optional[int] = None,
@@ -204,26 +190,9 @@ class ImplicitALS(MatrixFactorization):
         transactions (`UserHistory.from_interactions`).  With neither, this is the unweighted
         fit and its bits."""
         _lib.require_gpu(self.item_embeddings.weight)
-        u = user_ids.detach().cpu().numpy() if isinstance(user_ids, torch.Tensor) else user_ids
-        i = item_ids.detach().cpu().numpy() if isinstance(item_ids, torch.Tensor) else item_ids
-        u, i = np.asarray(u).reshape(-1), np.asarray(i).reshape(-1)
-        w = self._interaction_weights(u.shape[0], weights, days_ago, time_decay)
-        hist = UserHistory.from_interactions(u, i, self.num_users, self.num_items, self.device,
-                                             weights=w)
+        hist = interactions_history(user_ids, item_ids, self.num_users, self.num_items,
+                                    self.device, weights, days_ago, time_decay)
         return self.fit_history(hist, iterations=iterations, track_loss=track_loss)
-
-    def _need_history(self, history: Optional[UserHistory] = None) -> UserHistory:
-        h = self.history if history is None else history
-        if h is None:
-            raise RuntimeError("no history: call fit_interactions / fit_history / set_history")
-        if not isinstance(h, UserHistory):
-            raise TypeError("history must be a UserHistory")
-        if h.num_items != self.num_items or h.num_users != self.num_users:
-            raise ValueError(f"history built for {h.num_users} users x {h.num_items} items, "
-                             f"model has {self.num_users} x {self.num_items}")
-        if h.device != self.device:
-            raise ValueError(f"history lives on {h.device}, the model on {self.device}")
-        return h
 
     def loss(self) -> float:
         """L(X, Y) over the model's history in float64, without a [U, I] matrix:
@@ -249,10 +218,10 @@ class ImplicitALS(MatrixFactorization):
     def user_factors(self, baskets, weights=None) -> torch.Tensor:
         """[n, d] fold-in vectors of n baskets (a list of item-id iterables, or a (ptr, idx) CSR
         with ascending unique rows): the user half-step against the fitted Y.  `weights`: a
-        weight per basket item ("three of these", "just viewed"), see `_weighted_basket_csr`."""
+        weight per basket item ("three of these", "just viewed"), see `basket_csr`."""
         gram = self._item_gram()
         _, Y = self._tables()
-        ptr, idx, n, w = self._weighted_basket_csr(baskets, weights)
+        ptr, idx, n, w = basket_csr(baskets, self.num_items, Y.device, weights)
         out = torch.empty(n, self.embedding_dim, dtype=torch.float32, device=Y.device)
         self._solve(ptr, idx, n, Y, gram, None, n, out, w)
         _lib.sync_check(Y.device)   # a CSR given by the caller may hold any id
@@ -267,13 +236,12 @@ class ImplicitALS(MatrixFactorization):
         gram = self._item_gram()
         _, Y = self._tables()
         dev, d = Y.device, self.embedding_dim
-        ptr, idx, n, w = self._weighted_basket_csr(baskets, weights)
+        ptr, idx, n, w = basket_csr(baskets, self.num_items, Y.device, weights)
         kk = min(k, self.num_items)
         if kk <= 0:
             return empty_topk(k, ptr[:n])
         if n == 0:
-            return (torch.empty(0, kk, dtype=torch.float32, device=dev),
-                    torch.empty(0, kk, dtype=torch.int64, device=dev))
+            return empty_rows(0, kk, dev)
         F = torch.empty(n, d, dtype=torch.float32, device=dev)
         self._solve(ptr, idx, n, Y, gram, None, n, F, w)
         rows = torch.arange(n, dtype=torch.int64, device=dev)
@@ -283,19 +251,15 @@ class ImplicitALS(MatrixFactorization):
         c = _lib.ctx(dev)
         if kk > 64:
             s = torch.empty(n, self.num_items, dtype=torch.float32, device=dev)
-            _lib.check(_lib.fn("hnm_dot_scores_f32")(
-                c, _lib.ptr(F), n, d, _lib.ptr(rows), n, _lib.ptr(Y), self.num_items, d, d,
-                _lib.ptr(ub), _lib.ptr(ib), _lib.ptr(gb), _lib.ptr(s), s.stride(0)),
-                "hnm_dot_scores_f32")
+            _lib.call("hnm_dot_scores_f32", c, _lib.ptr(F), n, d, _lib.ptr(rows), n, _lib.ptr(Y),
+                      self.num_items, d, d, _lib.ptr(ub), _lib.ptr(ib), _lib.ptr(gb), _lib.ptr(s),
+                      s.stride(0))
             out = dense_topk(s, kk, mptr, midx)
         else:
-            out_v = torch.empty(n, kk, dtype=torch.float32, device=dev)
-            out_i = torch.empty(n, kk, dtype=torch.int64, device=dev)
-            _lib.check(_lib.fn("hnm_dot_topk_f32")(
-                c, _lib.ptr(F), n, d, _lib.ptr(rows), n, _lib.ptr(Y), self.num_items, d, d,
-                _lib.ptr(ub), _lib.ptr(ib), _lib.ptr(gb), _lib.ptr(mptr), _lib.ptr(midx), kk,
-                _lib.ptr(out_v), _lib.ptr(out_i)), "hnm_dot_topk_f32")
-            out = (out_v, out_i)
+            out = empty_rows(n, kk, dev)
+            _lib.call("hnm_dot_topk_f32", c, _lib.ptr(F), n, d, _lib.ptr(rows), n, _lib.ptr(Y),
+                      self.num_items, d, d, _lib.ptr(ub), _lib.ptr(ib), _lib.ptr(gb),
+                      _lib.ptr(mptr), _lib.ptr(midx), kk, _lib.ptr(out[0]), _lib.ptr(out[1]))
         _lib.sync_check(dev)
         return out
 

@@ -34,15 +34,18 @@ import torch
 
 from .. import _lib
 from ..evaluation import RecommendationMetrics
-from .base import (RecModule, UserHistory, _history_arrays, dense_topk, empty_topk, filter_csr,
-                   interaction_weights)
+from .base import (HistoryModel, RecModule, UserHistory, basket_csr, dense_topk, empty_rows,
+                   empty_topk, filter_csr, interactions_history)
 
 MAX_NEIGHBORS = 64   # one lane per neighbour
 FUSED_MAX_K = 64     # hnm_itemcf_topk_f32; above: dense rows + dense_topk
 
 
-class ItemCF(RecModule):
-    weighted = False     # WeightedItemCF: True (the hyperparameter "weighted" of its hparams)
+class ItemCF(HistoryModel, RecModule):
+    # WeightedItemCF: True (the hyperparameter "weighted" of its hparams)
+    weighted = takes_basket_weights = False
+    answers_baskets = back_fill_short_rows = True
+    _NO_HISTORY = "no history: call set_history (or fit_interactions) first"
 
     def __init__(self, num_users: int, num_items: int, num_neighbors: int = 64,
                  shrink: float = 0.0, max_history: int = 0, top_k: int = 12):
@@ -61,7 +64,6 @@ class ItemCF(RecModule):
         self.register_buffer("neighbor_idx", torch.full(shape, -1, dtype=torch.int32))
         self.register_buffer("neighbor_val", torch.zeros(shape, dtype=torch.float32))
         self.register_buffer("item_count", torch.zeros(self.num_items, dtype=torch.int64))
-        self.history: Optional[UserHistory] = None
         self._is_fitted: Optional[bool] = False   # None: unknown (a loaded state), looked up once
         self.metrics = RecommendationMetrics(top_k=self.top_k)
 
@@ -82,18 +84,6 @@ class ItemCF(RecModule):
                                "fitted state_dict")
 
     # ------------------------------------------------------------------ fitting
-    def set_history(self, history: Optional[UserHistory]):
-        """The history `recommend*` and `predict_all_items` read a user's row from."""
-        if history is not None:
-            if not isinstance(history, UserHistory):
-                raise TypeError("history must be a UserHistory")
-            if history.num_items != self.num_items or history.num_users != self.num_users:
-                raise ValueError(f"history built for {history.num_users} users x "
-                                 f"{history.num_items} items, model has {self.num_users} x "
-                                 f"{self.num_items}")
-        self.history = history
-        return self
-
     def _row_weights(self, history: UserHistory):
         """The weights a history row is served with: `hist_w` for a weighted model (None when the
         history has none: served unweighted), None for a plain one."""
@@ -108,26 +98,18 @@ class ItemCF(RecModule):
             raise ValueError("a weighted ItemCF is fitted on a history with weights "
                              "(UserHistory.from_interactions(..., weights=))")
         _lib.require_gpu(self.neighbor_idx)
-        self.set_history(history)
+        h = self.set_history(history)._need_history()
         dev = self.device
-        if history.device != dev:
-            raise ValueError(f"history lives on {history.device}, the model on {dev}")
         for name, dtype in (("neighbor_idx", torch.int32), ("neighbor_val", torch.float32),
                             ("item_count", torch.int64)):
             t = getattr(self, name)
             if t.dtype != dtype or not t.is_contiguous():
                 setattr(self, name, t.to(dtype).contiguous())
-        tail = (self.num_users, self.num_items, self.num_neighbors, self.shrink, self.max_history,
-                int(_window), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
-                _lib.ptr(self.item_count))
-        if self.weighted:
-            _lib.check(_lib.fn("hnm_itemcf_fit_weighted_f32")(
-                _lib.ctx(dev), _lib.ptr(history.hist_ptr), _lib.ptr(history.hist_idx),
-                _lib.ptr(history.hist_w), *tail), "hnm_itemcf_fit_weighted_f32")
-        else:
-            _lib.check(_lib.fn("hnm_itemcf_fit_f32")(
-                _lib.ctx(dev), _lib.ptr(history.hist_ptr), _lib.ptr(history.hist_idx), *tail),
-                "hnm_itemcf_fit_f32")
+        _lib.call_weighted(
+            "hnm_itemcf_fit_f32", 3, self._row_weights(h), _lib.ctx(dev), _lib.ptr(h.hist_ptr),
+            _lib.ptr(h.hist_idx), self.num_users, self.num_items, self.num_neighbors, self.shrink,
+            self.max_history, int(_window), _lib.ptr(self.neighbor_idx),
+            _lib.ptr(self.neighbor_val), _lib.ptr(self.item_count))
         _lib.sync_check(dev)
         self._is_fitted = True
         return self
@@ -148,51 +130,26 @@ class ItemCF(RecModule):
                              "weights or days_ago")
         if not self.weighted:   # a weighted model validates its arguments first (fit_history asks)
             _lib.require_gpu(self.neighbor_idx)
-        u = user_ids.detach().cpu().numpy() if isinstance(user_ids, torch.Tensor) else user_ids
-        i = item_ids.detach().cpu().numpy() if isinstance(item_ids, torch.Tensor) else item_ids
-        u, i = np.asarray(u).reshape(-1), np.asarray(i).reshape(-1)
-        w = None
-        if self.weighted:
-            w = interaction_weights(u.shape[0], weights, days_ago, time_decay)
-            w = np.ones(u.shape[0], np.float64) if w is None else w
-        hist = UserHistory.from_interactions(u, i, self.num_users, self.num_items, self.device,
-                                             weights=w)
+        # a plain model has refused weights and days_ago above and reads no time_decay
+        hist = interactions_history(user_ids, item_ids, self.num_users, self.num_items, self.device,
+                                    weights, days_ago, time_decay if self.weighted else 0.0,
+                                    unit_weights=self.weighted)
         return self.fit_history(hist, _window=_window)
 
     # ------------------------------------------------------------------ answering
-    def _users(self, user_ids):
-        """(int64 contiguous device ids, host_checked) -- RecModule._ids without a parameter."""
-        if not isinstance(user_ids, torch.Tensor):
-            user_ids = torch.as_tensor(user_ids)
-        user_ids = user_ids.reshape(-1)
-        _lib.require_gpu(self.neighbor_idx)
-        host = not user_ids.is_cuda
-        if host and user_ids.numel() > 0:
-            lo, hi = int(user_ids.min()), int(user_ids.max())
-            if lo < 0 or hi >= self.num_users:
-                raise IndexError(f"index out of range in self (user_ids must be in "
-                                 f"[0, {self.num_users}))")
-        return user_ids.to(device=self.device, dtype=torch.int64).contiguous(), host
-
-    def _need_history(self) -> UserHistory:
-        if self.history is None:
-            raise RuntimeError("no history: call set_history (or fit_interactions) first")
-        if self.history.device != self.device:
-            raise ValueError(f"history lives on {self.history.device}, the model on {self.device}")
-        return self.history
+    def _table_and_rows(self, dev, hptr, hidx):
+        """The leading arguments of the scores and top-K entries, up to the history CSR."""
+        return (_lib.ctx(dev), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
+                self.num_items, self.num_neighbors, _lib.ptr(hptr), _lib.ptr(hidx))
 
     def _dense(self, hptr, hidx, rows: int, u: Optional[torch.Tensor], B: int,
                w: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[B, num_items] scores; `w` (fp32, aligned with hidx) selects the weighted entry."""
-        out = torch.empty(B, self.num_items, dtype=torch.float32, device=self.device)
-        head = (_lib.ctx(self.device), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
-                self.num_items, self.num_neighbors, _lib.ptr(hptr), _lib.ptr(hidx))
-        tail = (rows, _lib.ptr(u), B, _lib.ptr(out), out.stride(0) if B else self.num_items)
-        if w is None:
-            _lib.check(_lib.fn("hnm_itemcf_scores_f32")(*head, *tail), "hnm_itemcf_scores_f32")
-        else:
-            _lib.check(_lib.fn("hnm_itemcf_scores_weighted_f32")(*head, _lib.ptr(w), *tail),
-                       "hnm_itemcf_scores_weighted_f32")
+        dev = self.device
+        out = torch.empty(B, self.num_items, dtype=torch.float32, device=dev)
+        _lib.call_weighted("hnm_itemcf_scores_f32", 7, w, *self._table_and_rows(dev, hptr, hidx),
+                           rows, _lib.ptr(u), B, _lib.ptr(out),
+                           out.stride(0) if B else self.num_items)
         return out
 
     def _topk(self, hptr, hidx, rows: int, u: Optional[torch.Tensor], B: int, mptr, midx, k: int,
@@ -201,17 +158,10 @@ class ItemCF(RecModule):
         (fp32, aligned with hidx) selects the weighted entries."""
         dev = self.device
         if k <= FUSED_MAX_K:
-            out_v = torch.empty(B, k, dtype=torch.float32, device=dev)
-            out_i = torch.empty(B, k, dtype=torch.int64, device=dev)
-            head = (_lib.ctx(dev), _lib.ptr(self.neighbor_idx), _lib.ptr(self.neighbor_val),
-                    self.num_items, self.num_neighbors, _lib.ptr(hptr), _lib.ptr(hidx))
-            tail = (rows, _lib.ptr(u), B, _lib.ptr(mptr), _lib.ptr(midx), k, _lib.ptr(out_v),
-                    _lib.ptr(out_i))
-            if w is None:
-                _lib.check(_lib.fn("hnm_itemcf_topk_f32")(*head, *tail), "hnm_itemcf_topk_f32")
-            else:
-                _lib.check(_lib.fn("hnm_itemcf_topk_weighted_f32")(*head, _lib.ptr(w), *tail),
-                           "hnm_itemcf_topk_weighted_f32")
+            out_v, out_i = empty_rows(B, k, dev)
+            _lib.call_weighted("hnm_itemcf_topk_f32", 7, w, *self._table_and_rows(dev, hptr, hidx),
+                               rows, _lib.ptr(u), B, _lib.ptr(mptr), _lib.ptr(midx), k,
+                               _lib.ptr(out_v), _lib.ptr(out_i))
             return out_v, out_i
         # k > 64: the dense rows and the row top-k kernel; slots without a positive score
         # (zero scores, masked items) become (-inf, -1)
@@ -224,11 +174,11 @@ class ItemCF(RecModule):
     def predict_all_items(self, user_ids) -> torch.Tensor:
         """[B, num_items] scores of the users' history rows."""
         self._fitted()
-        u, host = self._users(user_ids)
+        u, host = self._ids(user_ids, self.num_users, flat=True)
         h = self._need_history()
         out = self._dense(h.hist_ptr, h.hist_idx, h.num_users, u, u.numel(),
                           self._row_weights(h))
-        self._check(self.device, host)
+        self._check(u.device, host)
         return out
 
     def recommend_with_scores(self, user_ids, filter_items=None, k: Optional[int] = None):
@@ -237,7 +187,7 @@ class ItemCF(RecModule):
         in (-inf, -1).  k is clamped to num_items."""
         self._fitted()
         k = self.top_k if k is None else k
-        u, host = self._users(user_ids)
+        u, host = self._ids(user_ids, self.num_users, flat=True)
         h = self._need_history()
         mptr, midx = filter_csr(u, filter_items, self.num_items, u.device)
         kk = min(k, self.num_items)
@@ -245,7 +195,7 @@ class ItemCF(RecModule):
             return empty_topk(k, u)
         out = self._topk(h.hist_ptr, h.hist_idx, h.num_users, u, u.numel(), mptr, midx, kk,
                          self._row_weights(h))
-        self._check(self.device, host)
+        self._check(u.device, host)
         return out
 
     def recommend(self, user_ids, filter_items=None) -> torch.Tensor:
@@ -263,75 +213,18 @@ class ItemCF(RecModule):
         # held-out purchases are scored against what the model was fitted on
         return self.forward(batch["user_ids"])
 
-    def _basket_csr(self, baskets):
-        """(ptr int64[n + 1], idx int32, n) on the device from a list of item-id iterables
-        (sorted and de-duplicated here; ids outside [-num_items, num_items) raise IndexError)
-        or a (ptr, idx) CSR whose rows already are ascending and unique."""
-        dev = self.device
-        if isinstance(baskets, tuple) and len(baskets) == 2 and all(
-                isinstance(x, (torch.Tensor, np.ndarray)) for x in baskets):
-            ptr = torch.as_tensor(baskets[0]).reshape(-1).to(torch.int64)
-            idx = torch.as_tensor(baskets[1]).reshape(-1).to(torch.int32)
-            if ptr.numel() < 1:
-                raise ValueError("a basket CSR needs ptr of at least one entry")
-            p = ptr.cpu()
-            if int(p[0]) != 0 or bool((p[1:] < p[:-1]).any()) or int(p[-1]) > idx.numel():
-                raise ValueError("basket ptr must start at 0, not decrease and end within idx")
-        else:
-            sets = [list(b) for b in baskets]
-            p, i = _history_arrays(range(len(sets)), sets, self.num_items)
-            ptr, idx = torch.from_numpy(p), torch.from_numpy(i)
-        if idx.numel() == 0:
-            idx = torch.zeros(1, dtype=torch.int32)
-        return ptr.to(dev).contiguous(), idx.to(dev).contiguous(), ptr.numel() - 1
-
-    def _weighted_basket_csr(self, baskets, weights):
-        """(ptr, idx, n, w): `_basket_csr` plus the fp32 weights aligned with idx (None without
-        `weights`, whatever the fit was: the unweighted entry, weight 1).  For a list of baskets,
-        `weights` is a list of per-basket sequences aligned with the items, and a repeated item's
-        weights are summed by `UserHistory.from_interactions`' rule; for a (ptr, idx) CSR it is a
-        flat array aligned with idx."""
-        if weights is None:
-            return (*self._basket_csr(baskets), None)
-        dev = self.device
-        if isinstance(baskets, tuple) and len(baskets) == 2 and all(
-                isinstance(x, (torch.Tensor, np.ndarray)) for x in baskets):
-            ptr, idx, n = self._basket_csr(baskets)
-            w = torch.as_tensor(weights).reshape(-1).to(torch.float32)
-            if w.numel() != torch.as_tensor(baskets[1]).numel():
-                raise ValueError("weights must be aligned with the CSR's idx")
-            if w.numel() == 0:
-                w = torch.zeros(1, dtype=torch.float32)
-            return ptr, idx, n, w.to(dev).contiguous()
-        sets = [list(b) for b in baskets]
-        ws = [list(x) for x in weights]
-        if len(ws) != len(sets) or any(len(a) != len(b) for a, b in zip(sets, ws)):
-            raise ValueError("weights must hold one sequence per basket, aligned with its items")
-        rows = np.repeat(np.arange(len(sets), dtype=np.int64),
-                         np.asarray([len(b) for b in sets], np.int64))
-        flat = np.fromiter((int(x) for b in sets for x in b), np.int64, count=len(rows))
-        bad = (flat >= self.num_items) | (flat < -self.num_items)
-        if bad.any():
-            raise IndexError(f"index {int(flat[bad][0])} is out of bounds for dimension 1 with "
-                             f"size {self.num_items}")
-        flat = np.where(flat < 0, flat + self.num_items, flat)
-        wflat = np.fromiter((float(x) for b in ws for x in b), np.float64, count=len(rows))
-        h = UserHistory.from_interactions(rows, flat, max(len(sets), 1), self.num_items, dev,
-                                          weights=wflat)
-        return h.hist_ptr[:len(sets) + 1].contiguous(), h.hist_idx, len(sets), h.hist_w
-
     def recommend_for_items(self, baskets, filter_seen: bool = True, k: Optional[int] = None, *,
                             weights=None):
         """(scores [n, k], items [n, k]) for n baskets of item ids -- visitors without a user
         index.  `filter_seen` removes each basket's own items from its answer.  `weights` (a
         weighted model only, else ValueError): a weight per basket entry, a repeated item's
-        summed, see `_weighted_basket_csr`."""
+        summed, see `basket_csr`."""
         if weights is not None and not self.weighted:
             raise ValueError("this ItemCF is not weighted: it takes no basket weights")
         self._fitted()
         _lib.require_gpu(self.neighbor_idx)
         k = self.top_k if k is None else k
-        ptr, idx, n, w = self._weighted_basket_csr(baskets, weights)
+        ptr, idx, n, w = basket_csr(baskets, self.num_items, self.device, weights)
         kk = min(k, self.num_items)
         if kk <= 0:
             return empty_topk(k, ptr[:n])
@@ -355,22 +248,16 @@ class ItemCF(RecModule):
     def scoring_route(self, user_ids) -> List[str]:
         """Per user "fused" (the LDS table) or "dense" (a workspace row): what
         `hnm_itemcf_topk_f32` does with that history length.  The caller cannot choose."""
-        u, _ = self._users(user_ids)
+        u, _ = self._ids(user_ids, self.num_users, flat=True)
         h = self._need_history()
         lens = (h.hist_ptr[u + 1] - h.hist_ptr[u]).cpu().tolist()
         c = _lib.ctx(self.device)
         out = []
         for n in lens:
             route = C.c_int(-1)
-            _lib.check(_lib.fn("hnm_itemcf_route")(c, self.num_neighbors, int(n),
-                                                   C.byref(route)), "hnm_itemcf_route")
+            _lib.call("hnm_itemcf_route", c, self.num_neighbors, int(n), C.byref(route))
             out.append("dense" if route.value == 1 else "fused")
         return out
-
-
-def empty_rows(B: int, k: int, device):
-    return (torch.empty(B, k, dtype=torch.float32, device=device),
-            torch.empty(B, k, dtype=torch.int64, device=device))
 
 
 class WeightedItemCF(ItemCF):
@@ -380,7 +267,7 @@ class WeightedItemCF(ItemCF):
     the call's `weights`.  `ItemCF.__init__` keeps its parameter list, so the flag is the class;
     a checkpoint whose hyper-parameters hold `weighted: True` is built as this class
     (`serving.create_model_from_checkpoint`)."""
-    weighted = True
+    weighted = takes_basket_weights = True
 
     def __init__(self, num_users: int, num_items: int, num_neighbors: int = 64,
                  shrink: float = 0.0, max_history: int = 0, top_k: int = 12,

@@ -27,7 +27,7 @@ import torch
 
 from .. import _lib
 from ..evaluation import RecommendationMetrics
-from .base import RecModule, UserHistory, empty_topk, filter_csr
+from .base import RecModule, UserHistory, empty_rows, empty_topk, filter_csr
 
 
 def _host_array(x, dtype):
@@ -146,11 +146,8 @@ class PopularityBaseline(RecModule):
             w = torch.from_numpy(np.exp(-self.time_decay * np.arange(D))).to(dev)
         count = torch.empty(self.num_items, dtype=torch.int64, device=dev)
         pop = torch.empty(self.num_items, dtype=torch.float64, device=dev)
-        c = _lib.ctx(dev)
-        _lib.check(_lib.fn("hnm_popularity_fit_f64")(c, _lib.ptr(items), n, _lib.ptr(days),
-                                                     _lib.ptr(w), self.num_items, D, int(_slab),
-                                                     _lib.ptr(count), _lib.ptr(pop)),
-                   "hnm_popularity_fit_f64")
+        _lib.call("hnm_popularity_fit_f64", _lib.ctx(dev), _lib.ptr(items), n, _lib.ptr(days),
+                  _lib.ptr(w), self.num_items, D, int(_slab), _lib.ptr(count), _lib.ptr(pop))
         _lib.sync_check(dev)  # an item id outside [0, num_items): IndexError
         self.count = count
         bought = torch.nonzero(count > 0).reshape(-1)         # ascending item id
@@ -182,12 +179,6 @@ class PopularityBaseline(RecModule):
         return self.fit_interactions(np.asarray(train_df["article_idx"]), users, days)
 
     # ------------------------------------------------------------------ answering
-    def _user_ids(self, user_ids) -> torch.Tensor:
-        if not isinstance(user_ids, torch.Tensor):
-            user_ids = torch.as_tensor(user_ids)
-        _lib.require_gpu(self._anchor)
-        return user_ids.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
-
     def recommend_with_scores(self, user_ids, filter_items=None, k: Optional[int] = None,
                               *, _chunk: int = 0):
         """(scores [B, k] f32, items [B, k] int64): per user the first k entries of the order
@@ -196,19 +187,17 @@ class PopularityBaseline(RecModule):
         num_items.  One `hnm_popularity_topk_f32` call."""
         self._fitted()
         k = self.top_k if k is None else k
-        u = self._user_ids(user_ids)
+        u, _ = self._ids(user_ids, None, flat=True)   # no user table: any id is a user
         mptr, midx = filter_csr(u, filter_items, self.num_items, u.device)
         kk = min(k, self.num_items)
         if kk <= 0:
             return empty_topk(k, u)
         B = u.numel()
-        out_v = torch.empty(B, kk, dtype=torch.float32, device=u.device)
-        out_i = torch.empty(B, kk, dtype=torch.int64, device=u.device)
-        c = _lib.ctx(u.device)
-        _lib.check(_lib.fn("hnm_popularity_topk_f32")(
-            c, _lib.ptr(self.order), _lib.ptr(self.order_val), self.order.numel(),
-            _lib.ptr(self.rank), self.num_items, _lib.ptr(mptr), _lib.ptr(midx), B, kk,
-            int(_chunk), _lib.ptr(out_v), _lib.ptr(out_i)), "hnm_popularity_topk_f32")
+        out_v, out_i = empty_rows(B, kk, u.device)
+        _lib.call("hnm_popularity_topk_f32", _lib.ctx(u.device), _lib.ptr(self.order),
+                  _lib.ptr(self.order_val), self.order.numel(), _lib.ptr(self.rank),
+                  self.num_items, _lib.ptr(mptr), _lib.ptr(midx), B, kk, int(_chunk),
+                  _lib.ptr(out_v), _lib.ptr(out_i))
         return out_v, out_i
 
     def forward(self, user_ids) -> torch.Tensor:

@@ -153,13 +153,18 @@ class Recommender:
         model and its bits.  Its history becomes the recommender's device history when the
         recommender has none."""
         if weights is not None or days_ago is not None or float(time_decay) != 0.0:
-            model = WeightedItemCF(self.num_users, self.num_items, **kw).to(self.device)
-            model.fit_interactions(user_ids, item_ids, weights=weights, days_ago=days_ago,
-                                   time_decay=time_decay)
-        else:
-            model = ItemCF(self.num_users, self.num_items, **kw).to(self.device)
-            model.fit_interactions(user_ids, item_ids)
-        self.add_model(ITEM_CF, model)
+            return self._add_fitted(ITEM_CF, WeightedItemCF(self.num_users, self.num_items, **kw),
+                                    user_ids, item_ids, weights=weights, days_ago=days_ago,
+                                    time_decay=time_decay)
+        return self._add_fitted(ITEM_CF, ItemCF(self.num_users, self.num_items, **kw),
+                                user_ids, item_ids)
+
+    def _add_fitted(self, name: str, model, user_ids, item_ids, **fit_kw):
+        """Fit `model` on the transactions, register it under `name` and adopt its history as
+        the recommender's device history when the recommender has none."""
+        model = model.to(self.device)
+        model.fit_interactions(user_ids, item_ids, **fit_kw)
+        self.add_model(name, model)
         if not self.user_history and self._history_dev is None:
             self._history_dev = model.history
         return model
@@ -171,13 +176,9 @@ class Recommender:
         `weights` / `days_ago` / `time_decay`: per-transaction confidence weights, as in
         `ImplicitALS.fit_interactions` (quantities, a recency decay).
         Its history becomes the recommender's device history when the recommender has none."""
-        model = ImplicitALS(self.num_users, self.num_items, **kw).to(self.device)
-        model.fit_interactions(user_ids, item_ids, weights=weights, days_ago=days_ago,
-                               time_decay=time_decay)
-        self.add_model(ALS, model)
-        if not self.user_history and self._history_dev is None:
-            self._history_dev = model.history
-        return model
+        return self._add_fitted(ALS, ImplicitALS(self.num_users, self.num_items, **kw), user_ids,
+                                item_ids, weights=weights, days_ago=days_ago,
+                                time_decay=time_decay)
 
     def load_checkpoints(self, checkpoint_dir: str, graph=None) -> List[str]:
         """`_load_models` (`serve.py:170-209`): every `**/*.ckpt`, name = parent dir."""
@@ -298,12 +299,12 @@ class Recommender:
         # on the GPU from the device-resident history (serve.py:350-352)
         users = torch.tensor(idx, dtype=torch.int64)
         hist = self._device_history() if filter_purchased else None
-        if isinstance(model, ItemCF) and model.history is None:  # built from a checkpoint
+        if model.back_fill_short_rows and model.history is None:  # built from a checkpoint
             model.set_history(self._device_history())
         with torch.no_grad():
             vals, items = model.recommend_with_scores(users, filter_items=hist, k=num_items)
         vals, items = vals.cpu().tolist(), items.cpu().tolist()
-        if isinstance(model, ItemCF):
+        if model.back_fill_short_rows:
             def fill(rows):
                 with torch.no_grad():
                     pv, pi = self.models[BASELINE].recommend_with_scores(
@@ -324,10 +325,9 @@ class Recommender:
         another model."""
         self._check_num_items(num_items)
         name, model = self._resolve_model(model_name)
-        if not isinstance(model, (ItemCF, ImplicitALS)):
+        if not model.answers_baskets:
             raise ValueError(f"model {name} cannot answer from a basket of items")
-        if item_weights is not None and not (isinstance(model, ImplicitALS)
-                                             or getattr(model, "weighted", False)):
+        if item_weights is not None and not model.takes_basket_weights:
             raise ValueError(f"model {name} takes no item weights (only {ALS} and a weighted "
                              f"{ITEM_CF} do)")
         given = [int(i) for i in item_ids]
@@ -344,7 +344,7 @@ class Recommender:
             else:
                 vals, items = model.recommend_for_items([basket], filter_seen=True, k=num_items)
         vals, items = vals.cpu().tolist(), items.cpu().tolist()
-        if isinstance(model, ImplicitALS):
+        if not model.back_fill_short_rows:
             # every row is full: nothing to back-fill; a basket that leaves fewer than num_items
             # items ends in masked entries at -inf (the dot top-K's convention): not listed
             n = next((j for j, v in enumerate(vals[0]) if v == float("-inf")), len(vals[0]))

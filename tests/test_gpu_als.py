@@ -22,6 +22,8 @@ import scipy.linalg
 import torch
 
 import als_oracle as AO
+from als_raw import (ALPHA, DEV, FI, FU, REG, bits, dev, new_model, raw_solve, rel_err, strided,
+                     tables)
 from hnm_recommendation_amd import (ImplicitALS, MatrixFactorization, NeuralCF, UserHistory,
                                     _lib)
 from hnm_recommendation_amd import synthetic as syn
@@ -31,40 +33,13 @@ from hnm_recommendation_amd.serving import (Recommender, create_model_from_check
 from parity import assert_scores_close
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 GRAM_ROWS = 2048          # hnm.h: rows per Gram partial
-
-
-def bits(a):
-    if isinstance(a, torch.Tensor):
-        a = a.cpu().numpy()
-    return np.ascontiguousarray(a).view(np.int32)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def strided(a, ld):
-    """A device [rows, ld] buffer (NaN in the padding) whose first columns hold `a`."""
-    buf = torch.full((a.shape[0], ld), float("nan"), dtype=torch.float32, device=DEV)
-    buf[:, :a.shape[1]] = dev(a)
-    return buf
 
 
 def raw_gram(buf, rows, d):
     out = torch.full((d, d), float("nan"), dtype=torch.float32, device=DEV)
     st = _lib.fn("hnm_als_gram_f32")(_lib.ctx(DEV), _lib.ptr(buf), rows, buf.stride(0), d,
                                      _lib.ptr(out))
-    return st, out
-
-
-def raw_solve(ptr, idx, n_rows, buf, tab_rows, d, gram, alpha, reg, row_ids, B, ldo=None):
-    ldo = d if ldo is None else ldo
-    out = torch.full((max(B, 1), ldo), 7.0, dtype=torch.float32, device=DEV)
-    st = _lib.fn("hnm_als_solve_rows_f32")(
-        _lib.ctx(DEV), _lib.ptr(ptr), _lib.ptr(idx), n_rows, _lib.ptr(buf), tab_rows,
-        buf.stride(0), d, _lib.ptr(gram), alpha, reg, _lib.ptr(row_ids), B, _lib.ptr(out), ldo)
     return st, out
 
 
@@ -135,11 +110,6 @@ def solve_case(d, std, alpha, reg):
             A, b = AO.system32(idx[ptr[r]:ptr[r + 1]], T, G32, alpha, reg)
             x32[r] = scipy.linalg.solve(A, b, assume_a="pos")
     return T, x64, rel_err(x32, x64)
-
-
-def rel_err(x, x64):
-    nz = np.abs(x64).max(1) > 0
-    return float((np.abs(x[nz] - x64[nz]).max(1) / np.abs(x64[nz]).max(1)).max())
 
 
 def device_case(d, std, alpha, reg):
@@ -241,10 +211,6 @@ def test_solve_statuses():
 
 
 # ------------------------------------------------------------------ fit
-FU, FI = 300, 200
-ALPHA, REG = 40.0, 0.01
-
-
 @functools.lru_cache(maxsize=None)
 def fit_data():
     """Zipf-0.9 items, 0-30 items a user; users u % 17 == 0 and items i % 23 == 0 stay empty."""
@@ -259,11 +225,6 @@ def fit_data():
     return users, items, ptr, idx
 
 
-def new_model(d, seed=0, **kw):
-    return ImplicitALS(FU, FI, embedding_dim=d, regularization=REG, alpha=ALPHA, seed=seed,
-                       **kw).to(DEV)
-
-
 @functools.lru_cache(maxsize=None)
 def fit_reference(d):
     _, _, ptr, idx = fit_data()
@@ -275,11 +236,6 @@ def fit_reference(d):
 def fitted(d, iterations=3, seed=0):
     users, items, _, _ = fit_data()
     return new_model(d, seed).fit_interactions(users, items, iterations=iterations)
-
-
-def tables(m):
-    return (m.user_embeddings.weight.detach().cpu().numpy(),
-            m.item_embeddings.weight.detach().cpu().numpy())
 
 
 @pytest.mark.parametrize("d", [16, 64])

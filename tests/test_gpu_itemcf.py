@@ -2,13 +2,8 @@
 basket serving and the popularity back-fill.
 
 There is no reference implementation, so everything is compared BITWISE against the numpy
-restatement of the contract (include/hnm.h) in this file:
-
-* fit: n and C over the kept users, sim = float32(C / (sqrt(float64(n_i) * n_j) + shrink)), the
-  N best per row in (sim desc, j asc) order, padded with (-1, 0.0f);
-* scores: fp32 sums over the history items in ascending order, plain adds;
-* top-K: the unmasked items with score > 0 in (score desc, item asc) order, padded with
-  (-inf, -1) -- from the fused route and from the dense one.
+restatement of the contract (include/hnm.h) in itemcf_oracle.py (fit, scores, and the top-K
+selection -- here from the fused route and from the dense one).
 """
 import functools
 
@@ -16,78 +11,16 @@ import numpy as np
 import pytest
 import torch
 
-from hnm_recommendation_amd import ItemCF, PopularityBaseline, UserHistory, _lib
+from hnm_recommendation_amd import ItemCF, PopularityBaseline, _lib
 from hnm_recommendation_amd import synthetic as syn
 from hnm_recommendation_amd.evaluation import (evaluate_model, evaluate_recommendations,
                                                truth_csr)
 from hnm_recommendation_amd.serving import Recommender, create_model_from_checkpoint
+from itemcf_gpu import (BE, BI, BN, BU, DEV, I_X, NI, NU, U_81, U_82, U_BULK, U_EMPTY, U_HELPER,
+                        U_ONE, assert_fit_equal, bits, filters, host_back_fill)
+from itemcf_oracle import NEG_INF, np_csr, np_fit, np_scores, np_topk
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-NEG_INF = float("-inf")
-
-
-def bits(a):
-    if isinstance(a, torch.Tensor):
-        a = a.cpu().numpy()
-    return np.ascontiguousarray(a).view(np.int32)
-
-
-# ------------------------------------------------------------------ the numpy restatement
-def np_csr(users, items, U, I):
-    key = np.unique(np.asarray(users, np.int64) * I + np.asarray(items, np.int64))
-    r, it = np.divmod(key, I)
-    ptr = np.zeros(U + 1, np.int64)
-    np.cumsum(np.bincount(r, minlength=U), out=ptr[1:])
-    return ptr, it.astype(np.int32)
-
-
-def np_fit(ptr, idx, U, I, N, shrink=0.0, max_history=0):
-    """(nbr_idx int32 [I, N], nbr_val f32 [I, N], n int64 [I], sim f32 [I, I], C) -- dense."""
-    lens = np.diff(ptr)
-    A = np.zeros((U, I), np.float64)                       # exact: small integers
-    A[np.repeat(np.arange(U), lens), idx] = 1
-    if max_history:
-        A = A[lens <= max_history]
-    C = (A.T @ A).astype(np.int64)
-    n = np.diag(C).copy()
-    np.fill_diagonal(C, 0)
-    nf = n.astype(np.float64)
-    den = np.sqrt(nf[:, None] * nf[None, :]) + shrink
-    sim = np.divide(C, den, out=np.zeros((I, I)), where=C > 0).astype(np.float32)
-    nbr_idx = np.full((I, N), -1, np.int32)
-    nbr_val = np.zeros((I, N), np.float32)
-    for i in range(I):
-        cand = np.nonzero(C[i] > 0)[0]
-        top = cand[np.lexsort((cand, -sim[i, cand]))][:N]
-        nbr_idx[i, :len(top)] = top
-        nbr_val[i, :len(top)] = sim[i, top]
-    return nbr_idx, nbr_val, n, sim, C
-
-
-def np_scores(nbr_idx, nbr_val, I, rows, descending=False):
-    """fp32, one plain add per (history item, neighbour), history items in ascending order."""
-    out = np.zeros((len(rows), I), np.float32)
-    for b, h in enumerate(rows):
-        for j in (sorted(h, reverse=True) if descending else sorted(h)):
-            ok = nbr_idx[j] >= 0
-            out[b, nbr_idx[j][ok]] += nbr_val[j][ok]      # distinct items: one add each
-    return out
-
-
-def np_topk(scores, masks, k):
-    B = scores.shape[0]
-    ids = np.full((B, k), -1, np.int64)
-    vals = np.full((B, k), NEG_INF, np.float32)
-    for b in range(B):
-        s = scores[b].copy()
-        if masks is not None and len(masks[b]):
-            s[np.asarray(sorted(masks[b]), np.int64)] = 0.0
-        cand = np.nonzero(s > 0)[0]
-        top = cand[np.lexsort((cand, -s[cand]))][:k]
-        ids[b, :len(top)] = top
-        vals[b, :len(top)] = s[top]
-    return vals, ids
 
 
 # ------------------------------------------------------------------ fit
@@ -109,13 +42,6 @@ def small_ref(shape, N, shrink):
 def fit_model(users, items, U, I, N, shrink=0.0, max_history=0, window=0):
     m = ItemCF(U, I, num_neighbors=N, shrink=shrink, max_history=max_history).to(DEV)
     return m.fit_interactions(users, items, _window=window)
-
-
-def assert_fit_equal(m, ref):
-    ridx, rval, rn = ref[:3]
-    assert np.array_equal(m.item_count.cpu().numpy(), rn)
-    assert np.array_equal(m.neighbor_idx.cpu().numpy(), ridx)
-    assert np.array_equal(bits(m.neighbor_val), bits(rval))
 
 
 S1 = (600, 300, 6000)
@@ -212,13 +138,6 @@ def test_fit_same_bits_on_every_run():
 
 
 # ------------------------------------------------------------------ scores and top-K
-BU, BI, BE, BN = 2000, 1000, 30000, 50
-# hand-made users after the synthetic ones, hand-made items after the synthetic ones
-U_EMPTY, U_ONE, U_HELPER, U_BULK, U_81, U_82 = (BU + j for j in range(6))
-I_X = BI                                     # bought by U_ONE and U_HELPER
-NU, NI = BU + 6, BI + 4
-
-
 @functools.lru_cache(maxsize=None)
 def big():
     users, items = syn.interactions(BU, BI, BE, seed=2)
@@ -262,18 +181,6 @@ def test_routes():
     assert by_user[U_BULK] == "dense" and by_user[U_82] == "dense"       # 82 * 50 = 4,100
     assert by_user[U_81] == "fused" and by_user[U_EMPTY] == "fused"      # 81 * 50 = 4,050
     assert route.count("dense") == 3
-
-
-def filters(kind, hist, batch):
-    if kind == "none":
-        return None, None
-    if kind == "history":
-        h = UserHistory({u: set(r) for u, r in enumerate(hist) if r}, NU, NI, DEV)
-        return h, [hist[u] for u in batch]
-    d = syn.filter_dict(batch, NI, per_user=23, seed=8)
-    for u in batch[::2]:                                   # and what the user already holds
-        d[int(u)] |= set(hist[u])
-    return d, [sorted(d[int(u)]) for u in batch]
 
 
 @pytest.mark.parametrize("kind", ["none", "dict", "history"])
@@ -403,17 +310,6 @@ def test_state_dict_round_trip_keeps_the_answers():
 
 
 # ------------------------------------------------------------------ serving, evaluation
-def host_back_fill(vals, ids, pop_vals, pop_ids):
-    out_v, out_i = [v for v, i in zip(vals, ids) if i >= 0], [i for i in ids if i >= 0]
-    for v, i in zip(pop_vals, pop_ids):
-        if len(out_i) == len(ids) or i < 0:
-            break
-        if i not in out_i:
-            out_v.append(v)
-            out_i.append(i)
-    return out_v, out_i
-
-
 def test_serving_item_cf_baskets_and_back_fill():
     U, I, _ = S1
     users, items, (ptr, idx) = small(S1)

@@ -23,30 +23,14 @@ import torch
 
 import als_oracle as AO
 import wals_oracle as WO
-from hnm_recommendation_amd import ImplicitALS, MatrixFactorization, UserHistory, _lib
+from als_raw import (ALPHA, DEV, FI, FU, REG, bits, dev, new_model, raw_solve, rel_err, strided,
+                     tables)
+from hnm_recommendation_amd import MatrixFactorization, UserHistory, _lib
 from hnm_recommendation_amd import synthetic as syn
 from hnm_recommendation_amd.serving import Recommender
 from parity import assert_scores_close
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-
-
-def bits(a):
-    if isinstance(a, torch.Tensor):
-        a = a.cpu().numpy()
-    return np.ascontiguousarray(a).view(np.int32)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def strided(a, ld):
-    """A device [rows, ld] buffer (NaN in the padding) whose first columns hold `a`."""
-    buf = torch.full((a.shape[0], ld), float("nan"), dtype=torch.float32, device=DEV)
-    buf[:, :a.shape[1]] = dev(a)
-    return buf
 
 
 def raw_gram(buf, rows, d):
@@ -55,15 +39,6 @@ def raw_gram(buf, rows, d):
                                      _lib.ptr(out))
     assert st == _lib.HNM_OK
     return out
-
-
-def raw_solve(ptr, idx, n_rows, buf, tab_rows, d, gram, alpha, reg, row_ids, B, ldo=None):
-    ldo = d if ldo is None else ldo
-    out = torch.full((max(B, 1), ldo), 7.0, dtype=torch.float32, device=DEV)
-    st = _lib.fn("hnm_als_solve_rows_f32")(
-        _lib.ctx(DEV), _lib.ptr(ptr), _lib.ptr(idx), n_rows, _lib.ptr(buf), tab_rows,
-        buf.stride(0), d, _lib.ptr(gram), alpha, reg, _lib.ptr(row_ids), B, _lib.ptr(out), ldo)
-    return st, out
 
 
 def raw_wsolve(ptr, idx, w, n_rows, buf, tab_rows, d, gram, alpha, reg, row_ids, B, ldo=None):
@@ -100,11 +75,6 @@ def solve_rows():
 def table(d, std):
     rng = np.random.default_rng(d * 7 + int(std * 10))
     return rng.normal(0, std, (NI, d)).astype(np.float32)
-
-
-def rel_err(x, x64):
-    nz = np.abs(x64).max(1) > 0
-    return float((np.abs(x[nz] - x64[nz]).max(1) / np.abs(x64[nz]).max(1)).max())
 
 
 def oracle_and_yardstick(w, T, alpha, reg):
@@ -336,10 +306,6 @@ def test_score_of_an_item_grows_with_its_weight(alpha, reg):
 
 
 # ------------------------------------------------------------------ the module
-FU, FI = 300, 200
-ALPHA, REG = 40.0, 0.01
-
-
 @functools.lru_cache(maxsize=None)
 def fit_data():
     """test_gpu_als.py's transactions (Zipf-0.9 items; users u % 17 == 0 and items i % 23 == 0
@@ -359,11 +325,6 @@ def fit_data():
     return users, items, qty, days, ptr, idx, w64.astype(np.float32)
 
 
-def new_model(d, seed=0, **kw):
-    return ImplicitALS(FU, FI, embedding_dim=d, regularization=REG, alpha=ALPHA, seed=seed,
-                       **kw).to(DEV)
-
-
 @functools.lru_cache(maxsize=None)
 def fit_reference(d):
     _, _, _, _, ptr, idx, w = fit_data()
@@ -376,11 +337,6 @@ def fitted(d, iterations=3):
     users, items, qty, days, *_ = fit_data()
     return new_model(d).fit_interactions(users, items, weights=qty, days_ago=days,
                                          time_decay=0.01, iterations=iterations)
-
-
-def tables(m):
-    return (m.user_embeddings.weight.detach().cpu().numpy(),
-            m.item_embeddings.weight.detach().cpu().numpy())
 
 
 @pytest.mark.parametrize("d", [16, 64])

@@ -2,14 +2,8 @@
 hnm_itemcf_topk_weighted_f32, `WeightedItemCF`, weighted baskets and the `Recommender`.
 
 Everything is compared BITWISE against the numpy restatement of the contract (include/hnm.h) in
-this file:
-
-* fit: w_max over the kept users' entries, s = 32768 / w_max, q = rint(w * s) in float64,
-  A_q^T A_q in integers (n_w on the diagonal), sim = float32(C_w / (sqrt(float64(n_i) * n_j) +
-  (shrink * s) * s)), the N best per row in (sim desc, j asc) order, padded with (-1, 0.0f),
-  item_count = kept users holding the item with q > 0;
-* scores: fp32 sums over the history items in ascending order of float32(w_j * val), plain adds;
-* top-K: test_gpu_itemcf.py's selection, from the fused route and from the dense one.
+itemcf_oracle.py (the weighted fit and scores; the top-K is the plain selection, here from the
+fused route and from the dense one).
 
 The shapes are test_gpu_itemcf.py's with a few hand-made users and items after the synthetic
 ones (exact ties, an item whose weights are all zero, the bulk buyer).
@@ -23,101 +17,11 @@ import torch
 from hnm_recommendation_amd import ItemCF, UserHistory, WeightedItemCF, _lib
 from hnm_recommendation_amd import synthetic as syn
 from hnm_recommendation_amd.serving import Recommender, create_model_from_checkpoint
+from itemcf_gpu import (BE, BI, BN, BU, DEV, I_X, NI, NU, U_81, U_82, U_BULK, U_EMPTY, U_HELPER,
+                        U_ONE, assert_fit_equal, bits, filters, host_back_fill)
+from itemcf_oracle import NEG_INF, np_csr, np_fit_w, np_scores_w, np_topk
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-NEG_INF = float("-inf")
-
-
-def bits(a):
-    if isinstance(a, torch.Tensor):
-        a = a.cpu().numpy()
-    return np.ascontiguousarray(a).view(np.int32)
-
-
-# ------------------------------------------------------------------ the numpy restatement
-def np_csr(users, items, U, I):
-    key = np.unique(np.asarray(users, np.int64) * I + np.asarray(items, np.int64))
-    r, it = np.divmod(key, I)
-    ptr = np.zeros(U + 1, np.int64)
-    np.cumsum(np.bincount(r, minlength=U), out=ptr[1:])
-    return ptr, it.astype(np.int32)
-
-
-def np_quantise(ptr, w, U, max_history=0):
-    """(q uint64 per entry, s float64, kept bool [U]); s = inf and q = 0 when w_max == 0."""
-    lens = np.diff(ptr)
-    keep = np.ones(U, bool) if not max_history else lens <= max_history
-    ke = keep[np.repeat(np.arange(U), lens)]
-    wmax = np.float64(w[ke].max()) if ke.any() else np.float64(0)
-    if wmax == 0:
-        return np.zeros(len(w), np.uint64), np.float64(np.inf), keep
-    s = np.float64(32768.0) / wmax
-    return np.rint(w.astype(np.float64) * s).astype(np.uint64), s, keep
-
-
-def np_fit_w(ptr, idx, w, U, I, N, shrink=0.0, max_history=0, exact_uint64=False):
-    """(nbr_idx int32 [I, N], nbr_val f32 [I, N], item_count int64 [I], sim f32 [I, I], C) --
-    dense.  The products are taken in float64 after asserting that every sum stays below 2^53
-    (then float64 is exact and equals the uint64 sums; `exact_uint64` takes them in uint64)."""
-    w = np.asarray(w, np.float32)
-    q, s, keep = np_quantise(ptr, w, U, max_history)
-    rows = np.repeat(np.arange(U), np.diff(ptr))
-    if exact_uint64:
-        A = np.zeros((U, I), np.uint64)
-        A[rows, idx] = q
-        A = A[keep]
-        C = A.T @ A
-    else:
-        A = np.zeros((U, I), np.float64)
-        A[rows, idx] = q
-        A = A[keep]
-        assert float((A * A).sum(0).max(initial=0)) < 2.0 ** 53      # n_w bounds every C_w
-        C = (A.T @ A).astype(np.uint64)
-    n = np.diag(C).copy()
-    np.fill_diagonal(C, 0)
-    count = (A > 0).sum(0).astype(np.int64)
-    nf = n.astype(np.float64)
-    shrink_ss = (np.float64(shrink) * s) * s if np.isfinite(s) else np.float64(0)
-    den = np.sqrt(nf[:, None] * nf[None, :]) + shrink_ss
-    sim = np.divide(C.astype(np.float64), den, out=np.zeros((I, I)), where=C > 0).astype(np.float32)
-    nbr_idx = np.full((I, N), -1, np.int32)
-    nbr_val = np.zeros((I, N), np.float32)
-    for i in range(I):
-        cand = np.nonzero(C[i] > 0)[0]
-        top = cand[np.lexsort((cand, -sim[i, cand]))][:N]
-        nbr_idx[i, :len(top)] = top
-        nbr_val[i, :len(top)] = sim[i, top]
-    return nbr_idx, nbr_val, count, sim, C
-
-
-def np_scores_w(nbr_idx, nbr_val, I, rows, wrows):
-    """fp32: per history item j in ascending order, one rounded product and one plain add per
-    neighbour.  rows / wrows: ascending item lists and their raw fp32 weights."""
-    out = np.zeros((len(rows), I), np.float32)
-    for b, (h, ws) in enumerate(zip(rows, wrows)):
-        assert list(h) == sorted(h)
-        for j, wj in zip(h, ws):
-            ok = nbr_idx[j] >= 0
-            prod = np.float32(wj) * nbr_val[j][ok]            # float32 * float32: rounded once
-            assert prod.dtype == np.float32
-            out[b, nbr_idx[j][ok]] += prod                    # distinct items: one add each
-    return out
-
-
-def np_topk(scores, masks, k):
-    B = scores.shape[0]
-    ids = np.full((B, k), -1, np.int64)
-    vals = np.full((B, k), NEG_INF, np.float32)
-    for b in range(B):
-        s = scores[b].copy()
-        if masks is not None and len(masks[b]):
-            s[np.asarray(sorted(masks[b]), np.int64)] = 0.0
-        cand = np.nonzero(s > 0)[0]
-        top = cand[np.lexsort((cand, -s[cand]))][:k]
-        ids[b, :len(top)] = top
-        vals[b, :len(top)] = s[top]
-    return vals, ids
 
 
 def pair_weights(n, seed):
@@ -148,13 +52,6 @@ def fit_plain(hist, N, shrink=0.0, max_history=0, window=0):
     m = ItemCF(hist.num_users, hist.num_items, num_neighbors=N, shrink=shrink,
                max_history=max_history).to(DEV)
     return m.fit_history(hist, _window=window)
-
-
-def assert_fit_equal(m, ref):
-    ridx, rval, rn = ref[:3]
-    assert np.array_equal(m.item_count.cpu().numpy(), rn)
-    assert np.array_equal(m.neighbor_idx.cpu().numpy(), ridx)
-    assert np.array_equal(bits(m.neighbor_val), bits(rval))
 
 
 def assert_same_table(a, b):
@@ -357,12 +254,6 @@ def test_raw_fit_argument_errors_bad_weights_and_all_zero():
 
 
 # ------------------------------------------------------------------ scores and top-K
-BU, BI, BE, BN = 2000, 1000, 30000, 50
-U_EMPTY, U_ONE, U_HELPER, U_BULK, U_81, U_82 = (BU + j for j in range(6))
-I_X = BI                                     # bought by U_ONE and U_HELPER
-NU, NI = BU + 6, BI + 4
-
-
 @functools.lru_cache(maxsize=None)
 def big():
     users, items = syn.interactions(BU, BI, BE, seed=2)
@@ -422,18 +313,6 @@ def test_routes_are_those_of_the_unweighted_entry():
     assert by_user[U_BULK] == "dense" and by_user[U_82] == "dense"       # 82 * 50 = 4,100
     assert by_user[U_81] == "fused" and by_user[U_EMPTY] == "fused"      # 81 * 50 = 4,050
     assert route.count("dense") == 3
-
-
-def filters(kind, hist, batch):
-    if kind == "none":
-        return None, None
-    if kind == "history":
-        h = UserHistory({u: set(r) for u, r in enumerate(hist) if r}, NU, NI, DEV)
-        return h, [hist[u] for u in batch]
-    d = syn.filter_dict(batch, NI, per_user=23, seed=8)
-    for u in batch[::2]:                                   # and what the user already holds
-        d[int(u)] |= set(hist[u])
-    return d, [sorted(d[int(u)]) for u in batch]
 
 
 @pytest.mark.parametrize("kind", ["none", "dict", "history"])
@@ -641,17 +520,6 @@ def test_checkpoint_round_trip_keeps_the_weighted_class():
     ids = torch.arange(100)
     a, b = m.recommend_with_scores(ids, k=12), src.recommend_with_scores(ids, k=12)
     assert torch.equal(a[1], b[1]) and np.array_equal(bits(a[0]), bits(b[0]))
-
-
-def host_back_fill(vals, ids, pop_vals, pop_ids):
-    out_v, out_i = [v for v, i in zip(vals, ids) if i >= 0], [i for i in ids if i >= 0]
-    for v, i in zip(pop_vals, pop_ids):
-        if len(out_i) == len(ids) or i < 0:
-            break
-        if i not in out_i:
-            out_v.append(v)
-            out_i.append(i)
-    return out_v, out_i
 
 
 def test_recommender_weighted_item_cf_item_weights_and_back_fill():
