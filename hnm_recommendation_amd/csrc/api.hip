@@ -44,17 +44,18 @@ extern "C" hnm_status hnm_ctx_create(int device, hnm_ctx** out) {
   c->scan_shape = 1;
   c->scan_pipe = 1;
   c->scan_sparse = 1;
-  if (hipMalloc((void**)&c->err_dev, 64) != hipSuccess) {
+  if (hipMalloc((void**)&c->err_dev, 128) != hipSuccess) {
     free(c);
     hnm_set_error("hnm_ctx_create: hipMalloc of the error word failed");
     return HNM_ENOMEM;
   }
-  HNM_HIP_CHECK(hipMemset(c->err_dev, 0, 64));
+  HNM_HIP_CHECK(hipMemset(c->err_dev, 0, 128));
   HNM_HIP_CHECK(hipEventCreateWithFlags(&c->chain_ev, hipEventDisableTiming));
   HNM_HIP_CHECK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
   HNM_HIP_CHECK(hipEventCreateWithFlags(&c->side_in, hipEventDisableTiming));
   HNM_HIP_CHECK(hipEventCreateWithFlags(&c->side_out, hipEventDisableTiming));
   // counters of the certified pre-filter live in the same allocation (8-byte aligned)
+  static_assert(8 + HNM_STATS_N * sizeof(unsigned long long) <= 128, "error word + counters");
   c->stats_dev = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->err_dev) + 8);
   *out = c;
   return HNM_OK;

@@ -39,7 +39,8 @@ struct hnm_ctx {
   int comm_owned;                  // 1: created by hnm_ctx_rccl_init, destroyed with the ctx
   unsigned long long* stats_dev;   // pre-filter counters: rows, candidates, fallback rows,
                                    // rows whose bound used the gated strided sample, and
-                                   // (last NCF call) the gate's predicted proxy candidates
+                                   // (last NCF call) the gate's predicted proxy candidates,
+                                   // Wide&Deep rows that ran the cascade's second phase
   int stats_on;                    // HNM_OPT_STATS (default 0: counting costs same-address atomics)
   // open two-phase top-K call (hnm_*_topk_begin_f32 ... hnm_*_topk_finish_f32): the
   // workspace holds the begin phase's tables until the matching finish, so every other
@@ -71,7 +72,7 @@ struct HnmDeviceGuard {
   HnmDeviceGuard& operator=(const HnmDeviceGuard&) = delete;
 };
 #define HNM_CTX_DEVICE(c) const HnmDeviceGuard hnm_device_guard_((c) ? (c)->device : -1)
-#define HNM_STATS_N 6  // pre-filter counters (hnm_ctx_prefilter_stats_ex)
+#define HNM_STATS_N 7  // pre-filter counters (hnm_ctx_prefilter_stats_ex)
 #define HNM_PEND_NCF_CERT 1
 #define HNM_PEND_NCF_EXACT 2
 #define HNM_PEND_DOT_CERT 3

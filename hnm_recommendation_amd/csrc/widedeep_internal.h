@@ -299,7 +299,8 @@ struct WdRescoreArgs {
   int* nfb;
   float* ov;
   int64_t* oi;
-  unsigned long long* stats;  // HNM_OPT_STATS: rows, candidates re-scored in fp32, fallback rows
+  unsigned long long* stats;  // HNM_OPT_STATS: rows, candidates re-scored in fp32, fallback rows;
+                              // stats[6]: rows that ran the best-first second phase
   // the refining stage (three-pass split-f16 tile, wd_tile_f16x3)
   const wh8* W2hl;
   const wh8* W3hl;

@@ -410,6 +410,7 @@ __global__ __launch_bounds__(256) void wdc_filter_kernel(WdRescoreArgs R, int32_
   if (b >= R.B) return;
   const int ns = R.ns[b];
   if (ns <= WDC_BF_MIN) return;  // single phase (or the exact kernel's row): the list is complete
+  if (R.stats && lane == 0) atomicAdd(R.stats + 6, 1ull);  // rows that run the second phase
   const int K = R.K;
   const int64_t rowbase = b * R.rstride;
   WaveTopK<1> T2;  // K <= 64 = WDC_BF distinct items

@@ -8,8 +8,11 @@ oracle of the GPU's fp32 score.  Such scores take a few dozen distinct values, s
 sit at every position of every top-K, and the library's total order (score descending, item
 id ascending) decides most rows.
 
-`dot_scores` / `ncf_scores` assert the magnitudes that make the argument hold instead of
-assuming them.  NaN never appears in any input here (the routes treat it differently by
+Wide&Deep joins them through BatchNorm statistics whose sqrt(running_var + eps) is 0.5, 1 or 2
+exactly in fp32 (see WD_EPS below): its intermediates are multiples of 2^-3.
+
+`dot_scores` / `ncf_scores` / `wd_scores` assert the magnitudes that make the argument hold
+instead of assuming them.  NaN never appears in any input here (the routes treat it differently by
 design).  The GPU modules share the case tables at the bottom with tests/test_cpu_lattice.py,
 which checks on the CPU that the inputs have the properties the GPU tests rely on.
 """
@@ -304,6 +307,214 @@ def ncf_scores(sd, users, items=None):
     return (s + 0.0).astype(np.float32)
 
 
+# ---------------------------------------------------------------------------- Wide&Deep
+# nn.BatchNorm1d in eval mode divides by sqrt(running_var + eps).  With eps = 1e-5 in fp32,
+# fl(fl(t - eps) + eps) == t for t in {0.25, 1, 4}: running_var = float32(t) - float32(eps) makes
+# the divisor 0.5, 1 or 2 exactly, in the folded form (a = gamma / sqrt(var + eps),
+# c = beta - mean * a) and in the unfolded one alike.  wd_state_dict asserts it bit for bit.
+WD_EPS = np.float32(1e-5)
+WD_SQRT = np.array([0.5, 1.0, 2.0], np.float32)
+WD_DENSITIES = {"emb": 0.3, "w": 0.05, "final": 0.15, "wide": 0.5}
+
+
+def _wd_bn(rng, n):
+    s = WD_SQRT[rng.integers(0, 3, n)]
+    var = (s * s).astype(np.float32) - WD_EPS
+    assert var.dtype == np.float32
+    assert np.array_equal(bits(var + WD_EPS), bits(s * s)), "running_var + eps is not the square"
+    assert np.array_equal(bits(np.sqrt(var + WD_EPS)), bits(s))
+    gamma = rng.choice(np.array([-2, -1, 0, 1, 2], np.float32), n, p=[0.1, 0.15, 0.1, 0.4, 0.25])
+    return {"weight": gamma.astype(np.float32), "bias": rng.integers(-2, 3, n).astype(np.float32),
+            "running_mean": rng.integers(-2, 3, n).astype(np.float32), "running_var": var}
+
+
+def wd_state_dict(U, I, d, deep_layers, num_user_features=0, num_item_features=0, densities=None,
+                  seed=0, wide_user_item=True):
+    """Wide&Deep state dict (key layout of synthetic.widedeep_state_dict) on the lattice: ternary
+    embeddings, Linear weights and feature Linears, integer biases in [-2, 2]; BatchNorm with
+    sqrt(var + eps) in {0.5, 1, 2}, integer gamma in {-2..2} (zeros and negatives included),
+    integer mean and beta in [-2, 2]; final_layer = [integer wide user weights | wide item weights
+    in {-1, 0, 1} | ternary feature weights | ternary deep part], integer bias.  Every intermediate
+    of a score is then a multiple of 2^-3 (one halving a layer at most).  wide_user_item=False:
+    the layout of a model built with use_wide_user_item=False (no one-hot wide part)."""
+    dn = dict(WD_DENSITIES, **(densities or {}))
+    Fu, Fi = num_user_features, num_item_features
+    rng = _rng(seed, U, I, d, len(deep_layers), Fu, Fi)
+    ints = lambda n: rng.integers(-2, 3, n).astype(np.float32)
+    sd = {}
+    if wide_user_item:
+        sd["wide_user_embedding.weight"] = _ternary(rng, (U, 1), dn["emb"])  # unused by forward
+        sd["wide_item_embedding.weight"] = _ternary(rng, (I, 1), dn["emb"])
+    if Fu > 0:
+        sd["wide_user_features.weight"] = _ternary(rng, (Fu, Fu), 0.5)
+        sd["wide_user_features.bias"] = ints(Fu)
+    if Fi > 0:
+        sd["wide_item_features.weight"] = _ternary(rng, (Fi, Fi), 0.5)
+        sd["wide_item_features.bias"] = ints(Fi)
+    sd["deep_user_embedding.weight"] = _ternary(rng, (U, d), dn["emb"])
+    sd["deep_item_embedding.weight"] = _ternary(rng, (I, d), dn["emb"])
+    if Fu > 0:
+        sd["deep_user_features.weight"] = _ternary(rng, (d, Fu), 0.5)
+        sd["deep_user_features.bias"] = ints(d)
+    if Fi > 0:
+        sd["deep_item_features.weight"] = _ternary(rng, (d, Fi), 0.5)
+        sd["deep_item_features.bias"] = ints(d)
+    prev = (2 + (Fu > 0) + (Fi > 0)) * d
+    for li, h in enumerate(deep_layers):
+        sd[f"deep_network.{4 * li}.weight"] = _ternary(rng, (h, prev), dn["w"])
+        sd[f"deep_network.{4 * li}.bias"] = ints(h)
+        for key, v in _wd_bn(rng, h).items():
+            sd[f"deep_network.{4 * li + 2}.{key}"] = v
+        sd[f"deep_network.{4 * li + 2}.num_batches_tracked"] = np.zeros((), np.int64)
+        prev = h
+    parts = []
+    if wide_user_item:
+        parts += [ints(U), _ternary(rng, I, dn["wide"])]
+    parts += [_ternary(rng, Fu, 0.5), _ternary(rng, Fi, 0.5), _ternary(rng, prev, dn["final"])]
+    sd["final_layer.weight"] = np.concatenate(parts).astype(np.float32)[None, :]
+    sd["final_layer.bias"] = ints(1)
+    return sd
+
+
+def wd_features(n, F, seed=0):
+    """[n, F] float32 feature rows with entries in {-1, 0, 1} (None for F == 0)."""
+    if F == 0:
+        return None
+    return _rng(seed, n, F).integers(-1, 2, (n, F)).astype(np.float32)
+
+
+def _wd_lin(sd):
+    return sorted(int(k.split(".")[1]) for k, v in sd.items()
+                  if k.startswith("deep_network.") and k.endswith(".weight") and np.ndim(v) == 2)
+
+
+def _wd_check_lattice(Z, lin):
+    """Every input of a score is on the lattice: integers everywhere, except running_var, for
+    which sqrt(var + eps) evaluated in fp32 is 0.5, 1 or 2.  Returns the divisors per layer."""
+    sq = {}
+    for k, v in Z.items():
+        if k.endswith("num_batches_tracked"):
+            continue
+        if k.endswith("running_var"):
+            s = np.sqrt(np.asarray(v, np.float32) + WD_EPS)
+            assert s.dtype == np.float32 and np.isin(s, WD_SQRT).all(), k
+            sq[int(k.split(".")[1]) - 2] = s.astype(np.float64)
+            continue
+        a = np.asarray(v, np.float64)
+        assert np.array_equal(a, np.round(a)), k
+        assert np.abs(a).max(initial=0) < 2 ** 20, k
+    return [sq[li] for li in lin]
+
+
+def wd_scores(sd, users, user_features=None, item_table=None):
+    """Exact Wide&Deep scores [B, I] (float32) of `users` against every item, in float64 in the
+    reference's unfolded form (Linear -> ReLU -> (x - mean) / sqrt(var + eps) * gamma + beta per
+    layer; wide terms; final bias), with the assertions that make it a bitwise oracle of ANY
+    fp32 evaluation: every input is on the lattice (_wd_check_lattice), 2^3 * (sum of |terms|)
+    behind every layer's values stays below 2^24, and the result equals an fp32 evaluation of
+    the FOLDED form the fused kernels use (W2 * a1, b2 + W2 c1, ..., w_d * a_last; a = gamma /
+    sqrt(var + eps), c = beta - mean * a) in two different summation orders.
+    user_features [B, Fu] / item_table [I, Fi]: integer feature rows (models built with them)."""
+    users = np.asarray(users)
+    if len(users) > 16:  # [rows, I, width] intermediates: a few rows at a time
+        uf = user_features
+        return np.concatenate([wd_scores(sd, users[i:i + 16], None if uf is None else uf[i:i + 16],
+                                         item_table) for i in range(0, len(users), 16)])
+    lin = _wd_lin(sd)
+    sq = _wd_check_lattice(sd, lin)
+    Z = {k: np.asarray(v, np.float64) for k, v in sd.items()}
+    eu, ei = Z["deep_user_embedding.weight"][users], Z["deep_item_embedding.weight"]
+    B, I, d = len(users), ei.shape[0], ei.shape[1]
+    U = Z["deep_user_embedding.weight"].shape[0]
+    wf = Z["final_layer.weight"][0]
+    Fu = Z["wide_user_features.weight"].shape[0] if "wide_user_features.weight" in Z else 0
+    Fi = Z["wide_item_features.weight"].shape[0] if "wide_item_features.weight" in Z else 0
+    assert (user_features is not None) == (Fu > 0) and (item_table is not None) == (Fi > 0)
+    # ---- wide part: per-user and per-item terms (and the sums of |terms| behind them)
+    wu, awu, wi, awi, off = np.zeros(B), np.zeros(B), np.zeros(I), np.zeros(I), 0
+    if "wide_user_embedding.weight" in Z:
+        wu, wi, off = wf[users], wf[U:U + I], U + I
+        awu, awi = np.abs(wu), np.abs(wi)
+    xu, axu, xi, axi = eu, np.abs(eu), ei, np.abs(ei)  # deep inputs [B, *] / [I, *]
+    if Fu:
+        f = np.asarray(user_features, np.float64)
+        assert f.shape == (B, Fu) and np.array_equal(f, np.round(f))
+        W, b = Z["wide_user_features.weight"], Z["wide_user_features.bias"]
+        wu = wu + (f @ W.T + b) @ wf[off:off + Fu]
+        awu = awu + (np.abs(f) @ np.abs(W).T + np.abs(b)) @ np.abs(wf[off:off + Fu])
+        W, b = Z["deep_user_features.weight"], Z["deep_user_features.bias"]
+        xu = np.concatenate([xu, f @ W.T + b], 1)
+        axu = np.concatenate([axu, np.abs(f) @ np.abs(W).T + np.abs(b)], 1)
+    off += Fu
+    if Fi:
+        f = np.asarray(item_table, np.float64)
+        assert f.shape == (I, Fi) and np.array_equal(f, np.round(f))
+        W, b = Z["wide_item_features.weight"], Z["wide_item_features.bias"]
+        wi = wi + (f @ W.T + b) @ wf[off:off + Fi]
+        awi = awi + (np.abs(f) @ np.abs(W).T + np.abs(b)) @ np.abs(wf[off:off + Fi])
+        W, b = Z["deep_item_features.weight"], Z["deep_item_features.bias"]
+        xi = np.concatenate([xi, f @ W.T + b], 1)
+        axi = np.concatenate([axi, np.abs(f) @ np.abs(W).T + np.abs(b)], 1)
+    off += Fi
+    wd_, bf = wf[off:], Z["final_layer.bias"][0]
+    # ---- layer 1 as its per-user and per-item halves (input order: e_u, e_i, user f., item f.)
+    W1, b1 = Z[f"deep_network.{lin[0]}.weight"], Z[f"deep_network.{lin[0]}.bias"]
+    cu_ = np.r_[0:d, 2 * d:2 * d + (d if Fu else 0)]
+    ci_ = np.setdiff1d(np.arange(W1.shape[1]), cu_)
+    assert len(cu_) == xu.shape[1] and len(ci_) == xi.shape[1]
+    pu, qi = xu @ W1[:, cu_].T, xi @ W1[:, ci_].T
+    apu, aqi = axu @ np.abs(W1[:, cu_]).T, axi @ np.abs(W1[:, ci_]).T
+    z = pu[:, None, :] + qi[None, :, :] + b1                       # [B, I, l1]
+    az = apu[:, None, :] + aqi[None, :, :] + np.abs(b1)
+    pre = []  # post-ReLU values of every layer, for the folded evaluation
+    for n, li in enumerate(lin):
+        if n > 0:
+            Wl, bl = Z[f"deep_network.{li}.weight"], Z[f"deep_network.{li}.bias"]
+            z, az = z @ Wl.T + bl, az @ np.abs(Wl).T + np.abs(bl)
+        assert 8 * az.max() < EXACT, (li, az.max())
+        z = np.maximum(z, 0)
+        p = f"deep_network.{li + 2}."
+        g, be, m = Z[p + "weight"], Z[p + "bias"], Z[p + "running_mean"]
+        z = (z - m) / sq[n] * g + be
+        az = (az + np.abs(m)) / sq[n] * np.abs(g) + np.abs(be)
+    deep = z @ wd_
+    amag = az @ np.abs(wd_) + awu[:, None] + awi[None, :] + abs(bf)
+    assert 8 * amag.max() < EXACT, amag.max()
+    s = wu[:, None] + wi[None, :] + deep + bf
+    assert np.array_equal(s * 8, np.round(s * 8))
+    out = (s + 0.0).astype(np.float32)  # an exact zero is +0, as in the oracle's fp32 chain
+    assert np.array_equal(out.astype(np.float64), s)
+    # ---- the folded form in fp32, two summation orders
+    F = np.float32
+    a = [(Z[f"deep_network.{li + 2}.weight"] / sq[n]).astype(F) for n, li in enumerate(lin)]
+    c = [(Z[f"deep_network.{li + 2}.bias"].astype(F) -
+          Z[f"deep_network.{li + 2}.running_mean"].astype(F) * a[n]) for n, li in enumerate(lin)]
+    for rev in (False, True):
+        o = (lambda x: x[..., ::-1]) if rev else (lambda x: x)
+        h = np.maximum((pu.astype(F)[:, None, :] + qi.astype(F)[None, :, :]) + b1.astype(F), F(0))
+        for n, li in enumerate(lin[1:], 1):
+            Wl = Z[f"deep_network.{li}.weight"].astype(F)
+            bl = Z[f"deep_network.{li}.bias"].astype(F)
+            Wf = Wl * a[n - 1][None, :]
+            bfold = bl + np.ascontiguousarray(o(Wl)) @ np.ascontiguousarray(o(c[n - 1]))
+            h = np.maximum(np.ascontiguousarray(o(h)) @ np.ascontiguousarray(o(Wf)).T + bfold, F(0))
+            assert h.dtype == F
+        wdf = wd_.astype(F) * a[-1]
+        bias = F(bf) + np.ascontiguousarray(o(wd_.astype(F))) @ np.ascontiguousarray(o(c[-1]))
+        fold = np.ascontiguousarray(o(h)) @ np.ascontiguousarray(o(wdf))
+        fold = (fold + (bias + wu.astype(F))[:, None]) + wi.astype(F)[None, :]
+        assert fold.dtype == F
+        assert np.array_equal(bits(fold + F(0)), bits(out)), ("folded fp32 form differs", rev)
+    return out
+
+
+def tie_group_sizes(scores, k, mask=None):
+    """Members of the tie group at position k, per row."""
+    d = apply_mask(scores, mask)
+    kth = -np.sort(-d, axis=1)[:, k - 1]
+    return (d == kth[:, None]).sum(1)
+
+
 def tie_fraction(scores, k, mask=None):
     """Fraction of rows whose reference has score[k - 1] == score[k]."""
     d = apply_mask(scores, mask)
@@ -440,3 +651,95 @@ NCF_CERT = {(I, B): NcfCase(I, B, seed=3 if (I, B) == (8192, 1) else 0)
 NCF_CERT_KS = (1, 12, 64)
 NCF_DEEP = NcfCase(8200, 33, (128, 64, 32, 16))
 NCF_TWO_PHASE = NcfCase(8200, 129)
+
+
+# Wide&Deep (tests/test_gpu_lattice_widedeep.py).  WDC_BF_MIN: the survivors above which a row of
+# the certified cascade refines best first in two phases, copied from
+# hnm_recommendation_amd/csrc/widedeep_rescore.hip; 4,096 items: the floor of wdc_eligible
+# (widedeep_cert.hip), below which -- and for a layer-1 width that is no multiple of 16 -- the
+# exact fused kernel answers.
+WDC_BF_MIN = 96
+WDC_MIN_ITEMS = 4096
+WD_D1 = {"emb": 0.3, "w": 0.05, "final": 0.15}
+WD_D2 = {"emb": 0.5, "w": 0.1, "final": 0.3}
+WD_D3 = {"emb": 0.5, "w": 0.2, "final": 0.5}
+
+
+class WdCase:
+    """One Wide&Deep model + user batch; densities and seed tuned per tower so that the
+    reference alone shows the tie pressure tests/test_cpu_lattice.py asserts."""
+
+    def __init__(self, name, tower, I, B, ks, densities, seed=0, Fu=0, Fi=0, wide=True,
+                 sparse=True):
+        self.id, self.tower, self.I, self.B, self.ks = name, tuple(tower), I, B, tuple(ks)
+        self.densities, self.seed, self.Fu, self.Fi, self.wide = densities, seed, Fu, Fi, wide
+        self.sparse = sparse  # sparse ties: the median tie group at k has at most 64 members
+        self.U, self.d = B + 7, 16
+        self.certified = tower[0] % 16 == 0 and I >= WDC_MIN_ITEMS
+
+    @functools.cached_property
+    def sd(self):
+        return wd_state_dict(self.U, self.I, self.d, self.tower, self.Fu, self.Fi, self.densities,
+                             self.seed, self.wide)
+
+    @functools.cached_property
+    def users(self):
+        return _rng(6, self.B).permutation(self.U)[:self.B].astype(np.int64)
+
+    @functools.cached_property
+    def user_table(self):  # [U, Fu]; the batch's rows: user_table[users]
+        return wd_features(self.U, self.Fu, seed=1)
+
+    @functools.cached_property
+    def item_table(self):  # [I, Fi]
+        return wd_features(self.I, self.Fi, seed=2)
+
+    @property
+    def user_features(self):
+        return None if self.Fu == 0 else self.user_table[self.users]
+
+    @functools.cached_property
+    def scores(self):
+        return wd_scores(self.sd, self.users, self.user_features, self.item_table)
+
+    @functools.lru_cache(maxsize=None)
+    def mask_csr(self, kind, k):
+        return masks(self.B, self.I, kind, self.scores, k, seed=8)
+
+    @functools.lru_cache(maxsize=None)
+    def ref(self, k, kind="none"):
+        return ref_topk(self.scores, k, self.mask_csr(kind, k))
+
+
+WD_CERT_KS = (1, 12, 64)
+WD_EXACT_KS = (1, 12, 63, 64)
+# the six certified tower shapes of tests/test_gpu_widedeep_shapes.py (CERT_TOWERS), sparse ties
+WD_CERT_FULL = ((48, 200, 100), (48, 50))  # every k x mask kind; the others: k = 12, no mask
+WD_CERT = {t: WdCase("cert-" + "-".join(map(str, t)), t, 4200, 9,
+                     WD_EXACT_KS if t in WD_CERT_FULL else WD_CERT_KS, dn, seed)
+           for t, dn, seed in (((48, 200, 100), WD_D1, 3), ((48, 100, 50), WD_D1, 0),
+                               ((48, 50, 20), WD_D2, 0), ((48, 20, 10), WD_D3, 0),
+                               ((48, 20), WD_D2, 0), ((48, 50), WD_D1, 1))}
+# layer 1 40 wide / 1,111 items: the exact fused kernel whatever the pre-filter switch
+WD_EXACT = WdCase("exact-40-100-50", (40, 100, 50), 1111, 9, WD_EXACT_KS, WD_D1, 0)
+WD_EXACT_WIDE = WdCase("exact-40-200-100", (40, 200, 100), 1111, 9, WD_EXACT_KS, WD_D1, 4)
+WD_B70 = WdCase("cert-48-50-B70", (48, 50), 4200, 70, (12,), WD_D1, 0)
+# tie groups of 136 .. 215 members at k = 64 in five of the nine rows: more than WDC_BF_MIN
+# survivors, so those rows run the cascade's second phase (wdc_filter_kernel)
+WD_BEST_FIRST = WdCase("bestfirst-48-50", (48, 50), 4200, 9, (12, 64), WD_D1, 0, sparse=False)
+WD_FEAT_EXACT = WdCase("feat-exact-40-100-50", (40, 100, 50), 1111, 9, WD_EXACT_KS, WD_D1, 0,
+                       Fu=3, Fi=4)
+WD_FEAT_CERT = WdCase("feat-cert-48-100-50", (48, 100, 50), 4200, 9, WD_CERT_KS, WD_D1, 2,
+                      Fu=3, Fi=4)
+# exact zeros among the scores, 17 of them inside the rows' top-64: the sign of zero is compared
+WD_NOWIDE = WdCase("nowide-48-50", (48, 50), 4200, 9, WD_CERT_KS, WD_D2, 2, wide=False)
+# no deep and no item term in the final layer: every item of a row ties.  Run with so many rows
+# that wd_partition (widedeep.hip) gives the scan ONE item partition -- 4,224 items a segment,
+# above its WDC_CAP = 4,096 appends -- every segment overflows and the row takes the exact kernel.
+WD_OVERFLOW = WdCase("overflow-48-20", (48, 20), 4200, 9, (12,), dict(WD_D2, final=0.0, wide=0.0),
+                     0, sparse=False)
+WDC_CAP = 4096
+WD_CASES = [*WD_CERT.values(), WD_EXACT, WD_EXACT_WIDE, WD_B70, WD_BEST_FIRST, WD_FEAT_EXACT,
+            WD_FEAT_CERT, WD_NOWIDE, WD_OVERFLOW]
+WD_DENSE_K = 100  # k > 64: dense scores + hnm_topk_rows_f32 (recommend_with_scores)
+WD_DENSE_K_CASES = (WD_EXACT, WD_CERT[(48, 200, 100)])

@@ -128,3 +128,100 @@ def test_certified_bound_is_narrower_than_a_level(case):
     if case.bias:
         e = e + 2.0 ** -22 * (np.abs(t["ub"][case.users]) + np.abs(t["ib"]).max())
     assert (2 * e).max() < 1.0, (2 * e).max()
+
+
+# ------------------------------------------------------------------ Wide&Deep
+WD_IDS = [c.id for c in L.WD_CASES]
+
+
+def wd_oracle_fp32(case, chunk=500):
+    """The fp32 numpy oracle over every (user, item) pair, in the reference's 500-item chunks
+    (with item features: forward on the expanded pairs, item_features = table[item])."""
+    from oracle import hnm_oracle as O
+    if case.Fi == 0:
+        return O.widedeep_predict_all_items(case.sd, case.users, case.user_features)
+    out = []
+    for s in range(0, case.I, chunk):
+        e = min(s + chunk, case.I)
+        eu, ei = np.repeat(case.users, e - s), np.tile(np.arange(s, e), case.B)
+        ef = np.repeat(case.user_features, e - s, axis=0)
+        out.append(O.widedeep_forward(case.sd, eu, ei, ef, item_features=case.item_table[ei])
+                   .reshape(case.B, e - s))
+    return np.concatenate(out, axis=1)
+
+
+@pytest.mark.parametrize("case", L.WD_CASES, ids=WD_IDS)
+def test_wd_inputs_exact_three_ways(case):
+    """wd_scores (float64, unfolded, with its own lattice / magnitude / folded-fp32 assertions)
+    == the fp32 numpy oracle == the torch CPU reference module, as uint32 bits.  The torch
+    module has no item features and always a one-hot wide part (its [pairs, U + I] one-hot
+    input: small batches only)."""
+    s = case.scores
+    assert s.dtype == np.float32 and s.shape == (case.B, case.I) and np.isfinite(s).all()
+    assert np.array_equal(s * 8, np.round(s * 8)) and np.abs(s).max() < 2048
+    assert np.array_equal(L.bits(wd_oracle_fp32(case)), L.bits(s))
+    if case.Fi == 0 and case.wide and case.B <= 16:
+        import torch
+        from oracle import torch_cpu as T
+        uf = None if case.Fu == 0 else torch.from_numpy(case.user_features)
+        with torch.no_grad():
+            t = T.widedeep_predict_all_items(T.as_torch(case.sd), torch.from_numpy(case.users), uf)
+        assert np.array_equal(L.bits(t.numpy()), L.bits(s))
+
+
+def test_wd_exactness_assertion_bites():
+    """The lattice assertions are live: running_var = 1 in place of 1 - eps (sqrt(1 + 1e-5) is
+    no lattice point), a weight of 0.3, and an entry of 2^22 are each refused."""
+    sd = L.wd_state_dict(12, 60, 8, (16, 8), seed=1)
+    users = np.arange(5)
+    L.wd_scores(sd, users)
+    for key, at, bad in (("deep_network.2.running_var", (3,), 1.0),
+                         ("deep_network.4.weight", (2, 5), 0.3),
+                         ("deep_item_embedding.weight", (7, 1), 2.0 ** 22)):
+        broken = dict(sd, **{key: sd[key].copy()})
+        broken[key][at] = bad
+        with pytest.raises(AssertionError):
+            L.wd_scores(broken, users)
+    # and the generator's own check of the BatchNorm construction: 0.25, 1 and 4 are the only
+    # squares it uses; each survives the round trip through running_var bit for bit
+    for t in (0.25, 1.0, 4.0):
+        v = np.float32(t) - L.WD_EPS
+        assert L.bits(v + L.WD_EPS) == L.bits(np.float32(t)) and v != np.float32(t)
+
+
+@pytest.mark.parametrize("case", L.WD_CASES, ids=WD_IDS)
+def test_wd_tie_pressure(case):
+    """Ties across position k in most rows; in the sparse-tie cases the median tie group at k
+    has at most 64 members, so a certified row is answered by the cascade and not by a fallback;
+    the best-first case has rows whose tie group alone exceeds the single-phase limit."""
+    for k in case.ks:
+        f = L.tie_fraction(case.scores, k)
+        assert f >= _min_tie(k), (case.id, k, f)
+        if case.sparse:
+            g = L.tie_group_sizes(case.scores, k)
+            assert np.median(g) <= 64, (case.id, k, g)
+    if case is L.WD_BEST_FIRST:
+        g = L.tie_group_sizes(case.scores, 64)
+        assert (g > L.WDC_BF_MIN).sum() >= 3 and g.max() <= 300, g
+
+
+def test_wd_case_table():
+    from test_gpu_widedeep_shapes import CERT_TOWERS
+    assert [list(t) for t in L.WD_CERT] == CERT_TOWERS and set(L.WD_CERT_FULL) <= set(L.WD_CERT)
+    assert all(c.certified for c in L.WD_CERT.values())
+    assert not L.WD_EXACT.certified and not L.WD_FEAT_EXACT.certified
+    assert L.WD_FEAT_CERT.certified and L.WD_NOWIDE.certified and L.WD_B70.certified
+    assert "wide_user_embedding.weight" not in L.WD_NOWIDE.sd
+    assert (L.WD_NOWIDE.ref(64)[0] == 0).any()  # exact zeros reach the top-K: their sign counts
+
+
+def test_wd_tie_group_mask_leaves_the_last_member():
+    """The same check as test_tie_group_mask_leaves_the_last_member on a Wide&Deep case."""
+    c, k = L.WD_CERT[(48, 50)], 12
+    ptr, idx = c.mask_csr("tie_group", k)
+    _, ri = c.ref(k, "tie_group")
+    for b in range(c.B):
+        row = c.scores[b]
+        grp = np.nonzero(row == -np.sort(-row)[k - 1])[0]
+        assert np.array_equal(idx[ptr[b]:ptr[b + 1]], grp[:-1])
+        assert grp[-1] in ri[b] and not (set(grp[:-1].tolist()) & set(ri[b].tolist()))

@@ -6,7 +6,7 @@ any order -- lattice.ncf_scores is a bitwise oracle for the small-catalogue kern
 scan, the certified f16 scan in every layout / loop / epilogue variant, the deep tower and the
 two-phase API.  Scores take ~70 values: most rows tie across position k, so the
 (score desc, id asc) order decides them (tests/test_cpu_lattice.py checks that on the CPU).
-Wide&Deep has no such oracle (its eval-mode BatchNorm scaling is exact on no lattice).
+Wide&Deep's oracle: tests/test_gpu_lattice_widedeep.py.
 """
 import ctypes as C
 import functools
