@@ -187,6 +187,13 @@ _SIGS = {
     # ctx, ptr, idx, w, n_rows, tab, tab_rows, ld, d, gram, alpha, reg, row_ids, B, out, ldo
     "hnm_als_solve_rows_weighted_f32": (_i32, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p,
                                                _f32, _f32, _p, _i64, _p, _i64]),
+    # ctx, ptr, idx, n_rows, tab, tab_rows, ld, d, gram, alpha, reg, row_ids, B, x (in/out), ldx,
+    # steps
+    "hnm_als_cg_rows_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _f32, _f32, _p,
+                                   _i64, _p, _i64, C.c_int]),
+    # the entry above with w after idx
+    "hnm_als_cg_rows_weighted_f32": (_i32, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p,
+                                            _f32, _f32, _p, _i64, _p, _i64, C.c_int]),
 }
 
 _lib = None

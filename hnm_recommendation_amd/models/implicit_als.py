@@ -20,7 +20,13 @@ Three HIP entries (`csrc/als.hip`, contract in `include/hnm.h`):
 * `hnm_als_solve_rows_weighted_f32` -- the same half-step with a weight per stored entry:
   (G + alpha sum w t t^T + reg I) x = sum (1 + alpha w) t.  A history with `hist_w` takes it in
   the fit (the transpose carries the weights) and in `refresh_users`; `user_factors` and
-  `recommend_for_items` take it when the call gives `weights`.
+  `recommend_for_items` take it when the call gives `weights`;
+* `hnm_als_cg_rows_f32` / `hnm_als_cg_rows_weighted_f32` (`csrc/als_cg.hip`) -- the same
+  systems, bit for bit, taken a few conjugate-gradient steps from the previous sweep's row
+  instead of solved exactly (Takacs, Pilaszy & Tikk 2011): `fit_history(..., solver="cg",
+  cg_steps=3)`.  An option of a fit only: fold-in, `refresh_users` and the cached item Gram stay
+  on the exact Cholesky entry, so after a CG fit the stored user rows are the approximate ones
+  the sweeps left and a refreshed row is the exact one.
 
 A fit is `iterations` sweeps (user step, then item step): no optimizer, no sampling, no
 learning rate.  The module IS a `MatrixFactorization` with zero biases: the same parameters and
@@ -40,10 +46,22 @@ from .base import (HistoryModel, UserHistory, basket_csr, dense_topk, empty_rows
 from .matrix_factorization import MatrixFactorization
 
 LOSS_PAIR_CHUNK = 1 << 20   # history pairs per float64 pass of loss()
+SOLVERS = ("cholesky", "cg")
+MAX_CG_STEPS = 32           # hnm.h: hnm_als_cg_rows_f32 takes steps in [1, 32]
 
 
 def supported_dim(d: int) -> bool:
     return 16 <= d <= 128 and d % 16 == 0
+
+
+def check_solver(solver, cg_steps):
+    """The validated (solver, cg_steps) of a fit: ("cholesky", None) or ("cg", steps)."""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, not {solver!r}")
+    if isinstance(cg_steps, bool) or int(cg_steps) != cg_steps \
+            or not 1 <= int(cg_steps) <= MAX_CG_STEPS:
+        raise ValueError(f"cg_steps must be an integer in [1, {MAX_CG_STEPS}]")
+    return (solver, int(cg_steps)) if solver == "cg" else (solver, None)
 
 
 class ImplicitALS(HistoryModel, MatrixFactorization):
@@ -66,6 +84,7 @@ class ImplicitALS(HistoryModel, MatrixFactorization):
         self.regularization, self.alpha = float(regularization), float(alpha)
         self.iterations, self.seed = int(iterations), int(seed)
         self.loss_history: List[float] = []
+        self.fit_solver = ("cholesky", None)   # what the last fit ran: a fit's option, for logs
         self._gram: Optional[torch.Tensor] = None   # Y^T Y of the fitted item table (fold-in)
         with torch.no_grad():
             self.user_embeddings.weight.zero_()
@@ -112,6 +131,14 @@ class ImplicitALS(HistoryModel, MatrixFactorization):
             out.stride(0) if B else self.embedding_dim)
         return out
 
+    def _cg(self, ptr, idx, n_rows: int, tab, gram, x, steps: int, w=None):
+        """One CG half-step for every row, in place on `x` (its rows are the start vectors)."""
+        _lib.call_weighted(
+            "hnm_als_cg_rows_f32", 3, w, _lib.ctx(tab.device), _lib.ptr(ptr), _lib.ptr(idx),
+            n_rows, _lib.ptr(tab), tab.shape[0], tab.stride(0), self.embedding_dim, _lib.ptr(gram),
+            self.alpha, self.regularization, None, n_rows, _lib.ptr(x), x.stride(0), steps)
+        return x
+
     def _item_gram(self) -> torch.Tensor:
         _, Y = self._tables()
         if self._gram is None or self._gram.device != Y.device:
@@ -142,12 +169,19 @@ class ImplicitALS(HistoryModel, MatrixFactorization):
         return tptr, tusers.contiguous(), tw
 
     def fit_history(self, history: UserHistory, *, iterations: Optional[int] = None,
-                    track_loss: bool = False):
+                    track_loss: bool = False, solver: str = "cholesky", cg_steps: int = 3):
         """Fit on a `UserHistory` and keep it as the model's history: `iterations` sweeps of
         (user step, item step) from the seeded Y.  A history with weights (`hist_w`) is fitted
         with c_ui = 1 + alpha w_ui through the weighted entry, one without through the unweighted
         one.  `track_loss`: `loss()` after every sweep in `self.loss_history` (a monitoring pass
-        in float64 per sweep)."""
+        in float64 per sweep).
+
+        `solver="cg"`: both half-steps of every sweep take `cg_steps` (1..32) conjugate-gradient
+        steps from the row's value of the previous sweep instead of the exact Cholesky solve,
+        in place on X and Y (X starts at zeros, Y at the seeded table).  The sweeps still lower
+        the loss; the tables are not the exact-solve fit's.  `self.fit_solver` keeps what ran.
+        Fold-in (`user_factors`, `recommend_for_items`) and `refresh_users` stay exact."""
+        chosen = check_solver(solver, cg_steps)
         _lib.require_gpu(self.item_embeddings.weight)
         iters = self.iterations if iterations is None else int(iterations)
         if iters < 0:
@@ -163,14 +197,23 @@ class ImplicitALS(HistoryModel, MatrixFactorization):
             self.global_bias.zero_()
         self._gram = None
         self.loss_history = []
+        self.fit_solver = chosen
         tptr, tusers, tw = self._transpose(history)
         U, I = self.num_users, self.num_items
         gram = torch.empty(self.embedding_dim, self.embedding_dim, dtype=torch.float32, device=dev)
         for _ in range(iters):
             self._gram_of(Y, gram)
-            self._solve(history.hist_ptr, history.hist_idx, U, Y, gram, None, U, X, history.hist_w)
+            if chosen[0] == "cg":
+                self._cg(history.hist_ptr, history.hist_idx, U, Y, gram, X, chosen[1],
+                         history.hist_w)
+            else:
+                self._solve(history.hist_ptr, history.hist_idx, U, Y, gram, None, U, X,
+                            history.hist_w)
             self._gram_of(X, gram)
-            self._solve(tptr, tusers, I, X, gram, None, I, Y, tw)
+            if chosen[0] == "cg":
+                self._cg(tptr, tusers, I, X, gram, Y, chosen[1], tw)
+            else:
+                self._solve(tptr, tusers, I, X, gram, None, I, Y, tw)
             if track_loss:
                 self.loss_history.append(self.loss())
         _lib.sync_check(dev)
@@ -180,7 +223,7 @@ class ImplicitALS(HistoryModel, MatrixFactorization):
 
     def fit_interactions(self, user_ids, item_ids, *, weights=None, days_ago=None,
                          time_decay: float = 0.0, iterations: Optional[int] = None,
-                         track_loss: bool = False):
+                         track_loss: bool = False, solver: str = "cholesky", cg_steps: int = 3):
         """Fit from (user, item) interaction arrays or tensors (duplicates allowed; ids out of
         range raise IndexError): builds the `UserHistory`, keeps it, runs the sweeps.
 
@@ -188,11 +231,13 @@ class ImplicitALS(HistoryModel, MatrixFactorization):
         with `time_decay` >= 0 make it a weighted fit: a transaction weighs
         weights * exp(-time_decay * days_ago) (float64 on the host), a pair the sum of its
         transactions (`UserHistory.from_interactions`).  With neither, this is the unweighted
-        fit and its bits."""
+        fit and its bits.  `solver` / `cg_steps`: as in `fit_history`."""
+        check_solver(solver, cg_steps)
         _lib.require_gpu(self.item_embeddings.weight)
         hist = interactions_history(user_ids, item_ids, self.num_users, self.num_items,
                                     self.device, weights, days_ago, time_decay)
-        return self.fit_history(hist, iterations=iterations, track_loss=track_loss)
+        return self.fit_history(hist, iterations=iterations, track_loss=track_loss, solver=solver,
+                                cg_steps=cg_steps)
 
     def loss(self) -> float:
         """L(X, Y) over the model's history in float64, without a [U, I] matrix:
@@ -218,7 +263,8 @@ class ImplicitALS(HistoryModel, MatrixFactorization):
     def user_factors(self, baskets, weights=None) -> torch.Tensor:
         """[n, d] fold-in vectors of n baskets (a list of item-id iterables, or a (ptr, idx) CSR
         with ascending unique rows): the user half-step against the fitted Y.  `weights`: a
-        weight per basket item ("three of these", "just viewed"), see `basket_csr`."""
+        weight per basket item ("three of these", "just viewed"), see `basket_csr`.  Always the
+        exact (Cholesky) entry, whichever solver the fit used."""
         gram = self._item_gram()
         _, Y = self._tables()
         ptr, idx, n, w = basket_csr(baskets, self.num_items, Y.device, weights)
@@ -231,7 +277,8 @@ class ImplicitALS(HistoryModel, MatrixFactorization):
                             weights=None):
         """(scores [n, k], items [n, k]) for n baskets of item ids -- visitors without a user
         index: the fold-in vectors (`user_factors(baskets, weights)`) are the user table of the
-        dot-product top-K.  `filter_seen` removes each basket's own items from its answer."""
+        dot-product top-K.  `filter_seen` removes each basket's own items from its answer.  The
+        fold-in is the exact (Cholesky) entry, whichever solver the fit used."""
         k = self.top_k if k is None else k
         gram = self._item_gram()
         _, Y = self._tables()
@@ -266,7 +313,9 @@ class ImplicitALS(HistoryModel, MatrixFactorization):
     def refresh_users(self, user_ids, history: Optional[UserHistory] = None):
         """Recompute the stored factors of `user_ids` from `history` (default: the model's own)
         against the fitted Y -- a customer who bought something since the fit, without a refit.
-        A history with weights takes the weighted entry, as in the fit."""
+        A history with weights takes the weighted entry, as in the fit.  Always the exact
+        (Cholesky) entry: after a `solver="cg"` fit the stored rows are the approximate ones the
+        sweeps left, and a refreshed row is the exact one."""
         h = self._need_history(history)
         u, _ = self._ids(user_ids, self.num_users)
         gram = self._item_gram()

@@ -170,15 +170,16 @@ class Recommender:
         return model
 
     def add_als(self, user_ids, item_ids, weights=None, days_ago=None, time_decay: float = 0.0,
-                **kw) -> ImplicitALS:
+                solver: str = "cholesky", cg_steps: int = 3, **kw) -> ImplicitALS:
         """Fit an `ImplicitALS` (keywords: embedding_dim, regularization, alpha, iterations,
         seed, top_k) on the transactions' (user, item) pairs and register it as "implicit_als".
         `weights` / `days_ago` / `time_decay`: per-transaction confidence weights, as in
-        `ImplicitALS.fit_interactions` (quantities, a recency decay).
+        `ImplicitALS.fit_interactions` (quantities, a recency decay).  `solver` / `cg_steps` go
+        to the fit, not to the model: `solver="cg"` fits by conjugate-gradient half-steps.
         Its history becomes the recommender's device history when the recommender has none."""
         return self._add_fitted(ALS, ImplicitALS(self.num_users, self.num_items, **kw), user_ids,
                                 item_ids, weights=weights, days_ago=days_ago,
-                                time_decay=time_decay)
+                                time_decay=time_decay, solver=solver, cg_steps=cg_steps)
 
     def load_checkpoints(self, checkpoint_dir: str, graph=None) -> List[str]:
         """`_load_models` (`serve.py:170-209`): every `**/*.ckpt`, name = parent dir."""

@@ -859,6 +859,51 @@ hnm_status hnm_als_solve_rows_weighted_f32(hnm_ctx* ctx, const int64_t* ptr, con
                                            const float* gram, float alpha, float reg,
                                            const int64_t* row_ids, int64_t B, float* out,
                                            int64_t ldo);
+/* The half-step by conjugate gradients (Takacs, Pilaszy & Tikk 2011): `steps` CG steps on the
+ * row's system from a start vector, instead of the exact solve.  The arguments are
+ * hnm_als_solve_rows_f32's, except that out / ldo become the in/out x / ldx (ldx >= d): on entry
+ * row b of x (x + b * ldx) holds the start vector x0 for CSR row row_ids[b] (or row b), on return
+ * the result; and `steps` in [1, 32] is added.  A fit calls it with the table of the previous
+ * sweep as x (a warm start).  The system -- S, b0, A (its lower triangle, taken as the symmetric
+ * matrix) and b -- is hnm_als_solve_rows_f32's, bit for bit.  Then, in fp32:
+ *   x = x0;  r_i = b_i - (A x)_i;  p = r;  rs = r.r
+ *   repeat `steps` times:
+ *     if !(rs > 0) stop
+ *     q = A p;  pq = p.q
+ *     if !(pq > 0) stop
+ *     a = rs / pq;  x_i = fmaf(a, p_i, x_i);  r_i = fmaf(-a, q_i, r_i)
+ *     rn = r.r;  p_i = fmaf(rn / rs, p_i, r_i);  rs = rn
+ * Summation order, fixed at compile time and a function of d alone:
+ *   (A v)_i = ((P_0 + P_1) + P_2) + P_3,  P_w = the chain acc = fmaf(A_ij, v_j, acc) over
+ *             j = w d / 4, ..., (w + 1) d / 4 - 1 ascending, from 0.0f
+ *   u.v     = the butterfly sum over 64 slots l of z_l = fmaf(u_{l+64}, v_{l+64}, fl(u_l * v_l))
+ *             (d <= 64: z_l = fl(u_l * v_l)), elements >= d being zero: z <- z_l + z_{l ^ 32},
+ *             then ^ 16, 8, 4, 2, 1.
+ * No floating-point atomics: a row's bits depend on that row's inputs (its x0 included) and on
+ * `steps` -- not on B, on the other rows or on the run.  The row rules are
+ * hnm_als_solve_rows_f32's: a row without entries gives exact +0.0 (x0 is ignored); an idx entry
+ * or a row_ids entry out of range gives a NaN row and HNM_EOOB from hnm_ctx_check; the other rows
+ * are untouched; one workgroup owns a row whatever its length.  A non-finite x0 is the caller's
+ * problem: that row comes back non-finite, without an error.  steps outside [1, 32], x == NULL
+ * with work to do, reg <= 0, alpha < 0 or a non-finite value: HNM_EINVAL; d not a multiple of 16
+ * in [16, 128]: HNM_EUNSUPPORTED; B = 0 or n_rows = 0: HNM_OK, nothing launched, x untouched.
+ * Workspace: none. */
+hnm_status hnm_als_cg_rows_f32(hnm_ctx* ctx, const int64_t* ptr, const int32_t* idx,
+                               int64_t n_rows, const float* tab, int64_t tab_rows, int64_t ld,
+                               int64_t d, const float* gram, float alpha, float reg,
+                               const int64_t* row_ids, int64_t B, float* x, int64_t ldx, int steps);
+/* hnm_als_cg_rows_f32 on the weighted system: w f32, aligned with idx, right after it; S, b0,
+ * bw, A and b are hnm_als_solve_rows_weighted_f32's bit for bit, the recurrence and its
+ * summation order are the ones above.  With every weight 1.0f (or 2^e) the result is
+ * hnm_als_cg_rows_f32's bits at alpha (or at 2^e alpha) whenever 1.0f + that alpha is exact.  A
+ * negative or non-finite weight gives a NaN row and HNM_EINVAL from hnm_ctx_check; w == NULL
+ * with work to do: HNM_EINVAL.  Everything else is hnm_als_cg_rows_f32's. */
+hnm_status hnm_als_cg_rows_weighted_f32(hnm_ctx* ctx, const int64_t* ptr, const int32_t* idx,
+                                        const float* w, int64_t n_rows, const float* tab,
+                                        int64_t tab_rows, int64_t ld, int64_t d,
+                                        const float* gram, float alpha, float reg,
+                                        const int64_t* row_ids, int64_t B, float* x, int64_t ldx,
+                                        int steps);
 
 #ifdef __cplusplus
 }

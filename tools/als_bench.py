@@ -21,9 +21,17 @@ At the H&M shape (U = 1,371,980, I = 105,542, E = 31,788,324 synthetic interacti
     the unweighted entry's bits, the weighted answer is the same bits twice, finite, and its
     rows r = 0, n / 256, 2 n / 256, ... and its longest row agree with a float64
     `torch.linalg.solve` of the same systems.
+(g) the conjugate-gradient half-step (hnm_als_cg_rows_f32 and its weighted sibling) against the
+    Cholesky one, by (w)'s protocol -- the same CSR, tables and pair weights, calls interleaved
+    in this one process: user step and item step at d = 64 and d = 128, unweighted and weighted,
+    the Cholesky entry against the CG entry at 1, 3 and 5 steps.  The CG entry works in place, so
+    each timed CG call first restores its start vectors (the previous sweep's table) with one
+    device copy, which is timed alone as well.  Checked first: the CG answers are finite and the
+    same bits on a second run.  Then a whole `--sweeps` fit with each solver (cg_steps = 3) and
+    `loss()` of both fits.
 
 `--sections` picks the legs (default all, e.g. `--sections w`).  Each side of (a), (c), (e) and
-(w) is warmed up, then timed in interleaved rounds (order alternating)
+(w), (g) is warmed up, then timed in interleaved rounds (order alternating)
 between device synchronisations; medians and the spread of the per-round means are reported.
 """
 import argparse
@@ -49,7 +57,7 @@ ap.add_argument("--rows", type=int, default=syn.HM_INTERACTIONS)
 ap.add_argument("--sweeps", type=int, default=15)
 ap.add_argument("--cpu-budget", type=float, default=60.0)
 ap.add_argument("--torch-chunk", type=int, default=4096)
-ap.add_argument("--sections", default="abcdew")
+ap.add_argument("--sections", default="abcdewg")
 args = ap.parse_args()
 
 if not torch.cuda.is_available():
@@ -106,7 +114,7 @@ say(f"data: U = {U}, I = {I}, E = {args.rows} drawn, {hist.nnz} distinct (user, 
     f"{hist.nnz / I:.1f}, max {int(tlens.max())}")
 say(f"alpha = {ALPHA}, reg = {REG}")
 SEC = set(args.sections)
-if "w" in SEC:
+if "w" in SEC or "g" in SEC:
     g_w = torch.Generator(device="cpu").manual_seed(7)
     n_w = hist.hist_idx.numel()
     hist_w = (torch.randint(1, 9, (n_w,), generator=g_w).to(torch.float64)
@@ -114,7 +122,7 @@ if "w" in SEC:
     whist = copy.copy(hist)                                # the same CSR, with weights
     whist.hist_w = hist_w.to(torch.float32).to(dev)
     tw = ImplicitALS._transpose(whist)[2]
-    say(f"(w) pair weights count * exp(-0.01 days): min {float(whist.hist_w[:hist.nnz].min()):.4f}, "
+    say(f"(w, g) pair weights count * exp(-0.01 days): min {float(whist.hist_w[:hist.nnz].min()):.4f}, "
         f"mean {float(whist.hist_w[:hist.nnz].mean()):.4f}, max {float(whist.hist_w[:hist.nnz].max()):.4f}")
 
 
@@ -186,6 +194,62 @@ for d in (64, 128):
         names = list(wmed)
         say(f"    weighted / unweighted: user step {wmed[names[1]] / wmed[names[0]]:.3f}, item "
             f"step {wmed[names[3]] / wmed[names[2]]:.3f}")
+    if "g" in SEC:
+        x_cg, y_cg = torch.empty_like(X), torch.empty_like(Y)
+
+        def cg_user(steps, w=None):
+            x_cg.copy_(X)
+            return m._cg(hist.hist_ptr, hist.hist_idx, U, Y, gy, x_cg, steps, w)
+
+        def cg_item(steps, w=None):
+            y_cg.copy_(Y)
+            return m._cg(tptr, tusers, I, X, gx, y_cg, steps, w)
+
+        for tag, wu, wi in (("unweighted", None, None), ("weighted", whist.hist_w, tw)):
+            for steps in (1, 3, 5):
+                for f, w_ in ((cg_user, wu), (cg_item, wi)):
+                    a = f(steps, w_).clone()
+                    b = f(steps, w_)
+                    assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+                    assert bool(torch.isfinite(a).all())
+            _lib.sync_check(dev)
+            say(f"(g) d = {d}, {tag}: the CG answers (1, 3, 5 steps; user and item step) are "
+                "finite and the same bits on a second run")
+            gsides = {f"user step, Cholesky, {U} rows": lambda wu=wu: m._solve(
+                hist.hist_ptr, hist.hist_idx, U, Y, gy, None, U, x_out, wu)}
+            for steps in (1, 3, 5):
+                gsides[f"user step, CG {steps} steps (+ x0 copy)"] = \
+                    lambda steps=steps, wu=wu: cg_user(steps, wu)
+            gsides[f"x0 copy alone [{U}, {d}]"] = lambda: x_cg.copy_(X)
+            gsides[f"item step, Cholesky, {I} rows"] = lambda wi=wi: m._solve(
+                tptr, tusers, I, X, gx, None, I, y_out, wi)
+            for steps in (1, 3, 5):
+                gsides[f"item step, CG {steps} steps (+ x0 copy)"] = \
+                    lambda steps=steps, wi=wi: cg_item(steps, wi)
+            gmed = report(f"(g) CG against Cholesky half-steps, d = {d}, {tag}",
+                          interleaved(gsides, args.steps, args.rounds))
+            names = list(gmed)
+            say("    Cholesky / CG: user step " + ", ".join(
+                f"{gmed[names[0]] / gmed[names[k]]:.2f}x at {st} steps"
+                for k, st in ((1, 1), (2, 3), (3, 5))) + "; item step " + ", ".join(
+                f"{gmed[names[5]] / gmed[names[k]]:.2f}x at {st} steps"
+                for k, st in ((6, 1), (7, 3), (8, 5))))
+        del x_cg, y_cg
+        mf = ImplicitALS(U, I, embedding_dim=d, regularization=REG, alpha=ALPHA).to(dev)
+        for tag, h_ in (("unweighted", hist), ("weighted", whist)):
+            got = {}
+            for solver in ("cholesky", "cg"):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                mf.fit_history(h_, iterations=args.sweeps, solver=solver, cg_steps=3)
+                torch.cuda.synchronize()
+                got[solver] = (time.perf_counter() - t0, mf.loss())
+            say(f"(g) fit_history, {args.sweeps} sweeps, d = {d}, {tag}: cholesky "
+                f"{got['cholesky'][0]:.3f} s, loss {got['cholesky'][1]:.6e}; cg (3 steps) "
+                f"{got['cg'][0]:.3f} s, loss {got['cg'][1]:.6e}; time ratio "
+                f"{got['cholesky'][0] / got['cg'][0]:.2f}x, loss ratio cg / cholesky "
+                f"{got['cg'][1] / got['cholesky'][1]:.4f}")
+        del mf
     if "a" not in SEC:
         del x_out, y_out
         continue
