@@ -179,6 +179,10 @@ _SIGS = {
                                               _i64, _p, _i64]),
     "hnm_itemcf_topk_weighted_f32": (_i32, [_p, _p, _p, _i64, C.c_int, _p, _p, _p, _i64, _p, _i64,
                                             _p, _p, C.c_int, _p, _p]),
+    # ctx, list_val, list_idx, B, G, gstride, bstride, kc, mode, coef, num_items, mask_ptr,
+    # mask_idx, k, out_val, out_idx
+    "hnm_fuse_topk_f32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i64, C.c_int, C.c_int, _p, _i64,
+                                 _p, _p, C.c_int, _p, _p]),
     # ctx, tab, rows, ld, d, out [d, d]
     "hnm_als_gram_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p]),
     # ctx, ptr, idx, n_rows, tab, tab_rows, ld, d, gram, alpha, reg, row_ids, B, out, ldo
@@ -360,6 +364,7 @@ def sync_check(device):
 
 
 TIME_SCORE, TIME_SPMM = 1, 2
+HNM_FUSE_RANK, HNM_FUSE_SCORE, HNM_FUSE_CASCADE = 0, 1, 2   # hnm_fuse_topk_f32's modes
 
 
 def enable_timing(device, on=True):

@@ -7,6 +7,7 @@ from .base import UserHistory
 from .item_cf import ItemCF, WeightedItemCF
 from .implicit_als import ImplicitALS
 from .wide_deep import WideDeep
+from .ensemble import Ensemble
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
-           "ItemCF", "WeightedItemCF", "ImplicitALS", "UserHistory"]
+           "ItemCF", "WeightedItemCF", "ImplicitALS", "UserHistory", "Ensemble"]

@@ -28,6 +28,9 @@ article-metadata tables (out of scope: SURVEY §2):
 * `Recommender.add_als` -- no reference counterpart: an `ImplicitALS` fitted on the transactions
   under "implicit_als"; it answers users like every embedding model and baskets by fold-in
   (`get_recommendations_for_items(model_name="implicit_als")`; its rows are full: no back-fill).
+* `Recommender.add_ensemble` -- no reference counterpart: an `Ensemble` of registered models
+  under "ensemble" (reciprocal rank fusion, weighted scores or cascade of their top-K lists, fused
+  on the GPU); it answers through the same request paths as its members.
 """
 from __future__ import annotations
 
@@ -39,7 +42,7 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import torch
 
-from .models import (ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
+from .models import (Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
                      PopularityBaseline, WeightedItemCF, WideDeep)
 from .models.base import UserHistory
 
@@ -51,6 +54,7 @@ MAX_NUM_ITEMS = 100
 BASELINE = "popularity_baseline"  # serve.py:273: the name the reference registers it under
 ITEM_CF = "item_cf"
 ALS = "implicit_als"
+ENSEMBLE = "ensemble"
 
 # serve.py:238-248, tested in this order
 _DISPATCH = (("matrix_factorization", MatrixFactorization), ("neural_cf", NeuralCF),
@@ -180,6 +184,22 @@ class Recommender:
         return self._add_fitted(ALS, ImplicitALS(self.num_users, self.num_items, **kw), user_ids,
                                 item_ids, weights=weights, days_ago=days_ago,
                                 time_decay=time_decay, solver=solver, cg_steps=cg_steps)
+
+    def add_ensemble(self, member_names, weights=None, mode: str = "rrf",
+                     name: str = ENSEMBLE, **kw) -> Ensemble:
+        """Build an `Ensemble` (keywords: rank_constant, depth, top_k) from registered models,
+        in `member_names`' order, and register it under `name`; ValueError for a name that is
+        not registered.  It carries no metrics, so `"best"` resolves as before.  Requests go
+        through the existing paths: rows that run out of fused items are back-filled from the
+        popularity baseline when a member's are (`back_fill_short_rows`), and a basket is
+        answered when every member answers baskets."""
+        names = list(member_names)
+        unknown = [n for n in names if n not in self.models]
+        if unknown:
+            raise ValueError(f"models {unknown} are not available")
+        model = Ensemble([(n, self.models[n]) for n in names], weights=weights, mode=mode, **kw)
+        self.add_model(name, model)
+        return model
 
     def load_checkpoints(self, checkpoint_dir: str, graph=None) -> List[str]:
         """`_load_models` (`serve.py:170-209`): every `**/*.ckpt`, name = parent dir."""

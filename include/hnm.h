@@ -795,6 +795,54 @@ hnm_status hnm_itemcf_topk_weighted_f32(hnm_ctx* ctx, const int32_t* nbr_idx,
                                         const int64_t* mask_ptr, const int32_t* mask_idx, int k,
                                         float* out_val, int64_t* out_idx);
 
+/* ---- Fusion of overlapping top-K lists: an ensemble of models (no reference counterpart) ----
+ * hnm_topk_merge_f32 merges lists whose items are disjoint.  Here G models each give a list per
+ * row, the same item may stand in several of them, and its fused score depends on every list
+ * that holds it.
+ *
+ * Input.  Entry j (j < kc) of list g (g < G) of row b (b < B) sits at
+ * list_val / list_idx[g * gstride + b * bstride + j]: hnm_topk_merge_f32's layout.  Position j is
+ * rank j + 1.  An entry is EMPTY when idx < 0 or val is not finite (the (-inf, -1) tails of
+ * ItemCF and the popularity baseline, the -inf tails of the dot top-K): it contributes nothing.
+ * An entry with idx >= num_items raises the ctx error word (HNM_EOOB from hnm_ctx_check) and is
+ * skipped like an empty one.  The non-empty items of one list of one row must be distinct (every
+ * top-K entry of this library guarantees it); if they are not, that row's result is unspecified,
+ * and nothing outside the row's outputs is written.
+ *
+ * A non-empty entry (g, j) contributes
+ *   HNM_FUSE_RANK   coef[g * kc + j]     coef f32[G * kc]: the host's table, any rank discount
+ *                                        (reciprocal rank fusion: w_g / (c + j + 1)); no division
+ *                                        on the device
+ *   HNM_FUSE_SCORE  fl(coef[g] * val)    coef f32[G]: one fp32 rounding of the product
+ * and an item's fused score is the fp32 sum of its contributions in ascending g: it starts from
+ * the first contribution itself and continues with plain adds, never an fma.  coef is finite.
+ *
+ * Output, RANK and SCORE.  Row b of out_val / out_idx [B, k] holds the items that occur in at
+ * least one list of the row and are not in row b of the CSR mask (mask_ptr int64[B + 1] /
+ * mask_idx int32, rows ascending; both may be NULL), in (fused score descending, item
+ * ascending) order with their fused scores; slots past the last such item hold (-inf, -1).
+ * There is no score > 0 condition: dot-product scores may be negative.
+ *
+ * HNM_FUSE_CASCADE.  coef is ignored and may be NULL.  An item's key is (g*, j*): the lowest g
+ * whose list holds it, then its position there.  The output is the unmasked items in ascending
+ * key, each with the val of that first occurrence: list 0 first, then what list 1 adds, and so
+ * on -- a short list continued from the next one.
+ *
+ * Limits: 1 <= G <= 16, 1 <= kc <= 512, G * kc <= 2,048, 0 <= k <= 128; anything outside is
+ * HNM_EUNSUPPORTED (nothing is written).  A mode outside the three, or coef NULL in RANK or
+ * SCORE: HNM_EINVAL.  B = 0 or k = 0: HNM_OK, nothing launched.  One wave per row over an LDS
+ * table of the power of two >= 2 * G * kc slots (at most 32 KiB); no workspace, no float
+ * atomics: the sum's order is fixed by g, not by which lane arrives first, so the result is the
+ * same bits on every run. */
+#define HNM_FUSE_RANK 0
+#define HNM_FUSE_SCORE 1
+#define HNM_FUSE_CASCADE 2
+hnm_status hnm_fuse_topk_f32(hnm_ctx* ctx, const float* list_val, const int64_t* list_idx,
+                             int64_t B, int64_t G, int64_t gstride, int64_t bstride, int kc,
+                             int mode, const float* coef, int64_t num_items,
+                             const int64_t* mask_ptr, const int32_t* mask_idx, int k,
+                             float* out_val, int64_t* out_idx);
+
 /* ---- ImplicitALS: alternating least squares for implicit feedback (Hu, Koren & Volinsky
  * 2008; no reference counterpart) ----------------------------------------------------------
  * Gram matrix.  out f32[d, d] (contiguous) = tab^T tab over the first `rows` rows of tab (row
