@@ -390,6 +390,7 @@ HNM_OPT_NCF_TABLES = 7
 HNM_OPT_SCAN_SHAPE = 8
 HNM_OPT_SCAN_PIPE = 9
 HNM_OPT_SCAN_SPARSE = 10
+HNM_OPT_SCAN_ROW0 = 11
 
 
 def set_option(device, option, value):

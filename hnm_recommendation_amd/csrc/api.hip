@@ -44,6 +44,7 @@ extern "C" hnm_status hnm_ctx_create(int device, hnm_ctx** out) {
   c->scan_shape = 1;
   c->scan_pipe = 1;
   c->scan_sparse = 1;
+  c->scan_row0 = 1;
   if (hipMalloc((void**)&c->err_dev, 128) != hipSuccess) {
     free(c);
     hnm_set_error("hnm_ctx_create: hipMalloc of the error word failed");
@@ -132,6 +133,9 @@ extern "C" hnm_status hnm_ctx_set_option(hnm_ctx* ctx, int option, int64_t value
       return HNM_OK;
     case HNM_OPT_SCAN_SPARSE:
       ctx->scan_sparse = value != 0;
+      return HNM_OK;
+    case HNM_OPT_SCAN_ROW0:
+      ctx->scan_row0 = value != 0;
       return HNM_OK;
     default:
       hnm_set_error("hnm_ctx_set_option: unknown option %d", option);

@@ -35,6 +35,7 @@ struct hnm_ctx {
   int scan_shape;                  // HNM_OPT_SCAN_SHAPE (default 1)
   int scan_pipe;                   // HNM_OPT_SCAN_PIPE (default 1)
   int scan_sparse;                 // HNM_OPT_SCAN_SPARSE (default 1)
+  int scan_row0;                   // HNM_OPT_SCAN_ROW0 (default 1)
   void* comm;                      // RCCL communicator (ncclComm_t) of the C-side exchange
   int comm_owned;                  // 1: created by hnm_ctx_rccl_init, destroyed with the ctx
   unsigned long long* stats_dev;   // pre-filter counters: rows, candidates, fallback rows,

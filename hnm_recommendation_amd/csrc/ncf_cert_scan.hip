@@ -103,12 +103,30 @@ __device__ __forceinline__ h16 sparse_b(const f32x4 (&ca)[2][2], const f32x4 (&c
 // 50,944 B of LDS, three waves per SIMD; converts in the emitted loop 10 ahead, 6 under the first
 // instruction.  Kernel only 1.667 -> 1.626 ms, the step 1.833 -> 1.786 ms; matrix-pipe busy cycles
 // -9.7 %, the launch's cycles -3.0 % at an unchanged clock (profiles/ncf_scan_sparse_ab.txt).
-template <int MODE, bool DEEP = false, int SHAPE = 0, bool PIPE = false, bool SPARSE = false>
+// ROW0 (HNM_OPT_SCAN_ROW0, every pass of SHAPE 1 with the sparse epilogue): the same two sparse
+// instructions with wm in A rows 4 (2 user + n) = 0, 4, 8, 12 instead of 0-3 (user b's rows, 8 and
+// 12, at positions {2, 3}).  In the 16x16 D layout lane (c16, g4) holds rows 4 g4 + r, so the
+// pair's 64 test values are register r = 0 of all 64 lanes, lane 32 user + item: the append's bit
+// layout.  The THRESH test is one compare whose ballot IS the pass mask (four compares, three
+// s_or_b64 and a mask to lanes 0-15 before), each lane appends its own value (slot: its user's
+// count + its rank in that user's half of the mask, so slots, ids and values are the ones of the
+// four-register layout; the user's row offset, now per lane, goes into the vector offset), SAMPLE
+// and DEBUG store one value a lane (whole rows of 32 items, one store instruction a pair for
+// four).  The folded table g7 is [pair][64] in that lane order, one ds_read_b32 a lane.  Rows
+// 4 g4 + 1 .. 3 meet zero A rows; nothing reads them.  Same products, same accumulation order:
+// test values, candidate segments and debug outputs are bitwise those of ROW0 = false
+// (tests/test_gpu_ncf_scan_row0.py), whose kernels keep their instruction stream.  Pair loop of the
+// pipelined THRESH pass: VALU 54 -> 51, scalar ALU 8 -> 3; 152 VGPRs, no scratch, 50,944 B of LDS.
+// Kernel only 1.502 -> 1.467 ms, the step 1.744 -> 1.699 ms (profiles/ncf_scan_row0_ab.txt; unrolled
+// by four for immediate LDS offsets, another -0.3 %, inside the spread: not kept).
+template <int MODE, bool DEEP = false, int SHAPE = 0, bool PIPE = false, bool SPARSE = false,
+          bool ROW0 = false>
 __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kernel(ScanArgs A) {
   constexpr bool S16 = SHAPE == 1;  // layer 2 and the GMF on v_mfma_f32_16x16x32_f16
   static_assert(!(S16 && DEEP), "the deep scan has the 32x32x16 layout only");
   static_assert(!PIPE || (S16 && MODE == SCAN_THRESH), "the pipelined pair loop: THRESH, layout 1");
   static_assert(!SPARSE || S16, "the sparse epilogue: layout 1");
+  static_assert(!ROW0 || SPARSE, "test values in one register of 64 lanes: the sparse epilogue");
   // LDS row stride in halfs: 144 B (conflict-free b128 reads of the 32x32x16 operands: lane
   // (j, h) reads row j) / S16: 128 B with the row's 16-B chunks XOR-swizzled (s16_chunk)
   constexpr int RS = S16 ? 64 : 72;
@@ -216,9 +234,11 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
       for (int f = 0; f < 8; ++f) {
         const int t = f >> 1, gb = 2 * (g4 & 1) + (t >> 1), e = 2 * (2 * (g4 >> 1) + (t & 1)) + (f & 1);
         const _Float16 wv = A.wmh[16 * (e >> 2) + 4 * gb + (e & 3)];
-        ews[n][f] = (c16 == n || c16 == 2 + n) ? wv : (_Float16)0.f;
+        // ROW0: rows 4 n (user a) and 8 + 4 n (user b), i.e. 4 (2 user + n)
+        ews[n][f] = (ROW0 ? (c16 == 4 * n || c16 == 8 + 4 * n) : (c16 == n || c16 == 2 + n))
+                        ? wv : (_Float16)0.f;
       }
-    ewi = (c16 & 2) ? 0xEEEE : 0x4444;
+    ewi = (c16 & (ROW0 ? 8 : 2)) ? 0xEEEE : 0x4444;
   } else if constexpr (S16) {
     // the B operand of (user, item half n) is the lane's converted accumulators m = 0, 1 as one
     // h8: k = 8 g4 + e is unit 16 (e >> 2) + 4 g4 + (e & 3); A row 2 user + n holds wm in that
@@ -403,7 +423,9 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
           const float2 tc = ut[wave][row];
 #pragma unroll
           for (int n = 0; n < 2; ++n)
-            g7[(((row >> 1) * 16 + c16t) << 2) + ((row & 1) << 1) + n] =
+            // ROW0: [pair][64], a pair's 64 seeds in the order of the lanes that read them
+            g7[ROW0 ? (row >> 1) * 64 + (row & 1) * 32 + 16 * n + c16t
+                    : (((row >> 1) * 16 + c16t) << 2) + ((row & 1) << 1) + n] =
                 MODE == SCAN_DEBUG ? ga[m][n][r] * cg
                                    : (ga[m][n][r] * cg + sgn * fmaf(tc.y, djn[n], bjn[n])) - tc.x;
         }
@@ -465,6 +487,38 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
     auto pass_test = [&](const f32x4 d, const int u) {
       const int ua = u, ub = u + 1;
       const bool hasb = ub < nu;
+      if constexpr (ROW0) {
+        // lane 32 user + item holds the pair's test value d[0]: the one compare's ballot is the
+        // pass mask in the append's bit layout.  Like the OR of four below it may count a padded
+        // item of a partial last tile (and lanes of an absent user b: seed -inf), which vmask drops.
+        uint64_t m = __ballot(!(d[0] < 0.f));  // ordered compare: a NaN or -0 test value passes
+        if (m == 0) return;  // uniform
+        m &= vm32 | (hasb ? vm32 << 32 : 0ull);
+        if (masked && m) {  // uniform
+          const unsigned mba = (unsigned)hnm_readlane_i((int)mbits, ua);
+          const unsigned mbb = (unsigned)hnm_readlane_i((int)mbits, ub);
+          m &= ~((uint64_t)mba | ((uint64_t)mbb << 32));
+        }
+        if (m) {
+          // every lane appends its own value at the slot its rank in its user's half of the mask
+          // gives: the slots, ids and values of the four-register layout.  The user's row offset
+          // differs by lane here, so it goes into the vector offset.
+          const int ca = hnm_readlane_i(ccount, ua), cb = hnm_readlane_i(ccount, ub);
+          int pl = lane;
+          if constexpr (PIPE) asm volatile("v_mov_b32 %0, %1" : "=v"(pl) : "v"(lane));  // as below
+          const int uu = pl >> 5, it = pl & 31;
+          const unsigned mu = uu ? (unsigned)(m >> 32) : (unsigned)m;
+          const int ps = (uu ? cb : ca) + __builtin_popcount(mu & ((1u << it) - 1u));
+          if (((mu >> it) & 1u) && ps < A.capp) {
+            const int so = (uu ? ub : ua) * (int)segstride * 4;
+            __builtin_amdgcn_raw_buffer_store_b32((int)(base + it), segrs, so + ps * 4, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(d[0]), segdrs, so + ps * 4, 0, 0);
+          }
+          if (pl == ua) ccount += __builtin_popcount((unsigned)m);
+          if (pl == ub && hasb) ccount += __builtin_popcount((unsigned)(m >> 32));
+        }
+        return;
+      }
       // !(score + e_i < tau), ordered compares: a NaN or -0 test value passes
       const uint64_t b0 = __ballot(!(d[0] < 0.f)), b1 = __ballot(!(d[1] < 0.f));
       const uint64_t b2 = __ballot(!(d[2] < 0.f)), b3 = __ballot(!(d[3] < 0.f));
@@ -570,6 +624,11 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         }
       }
       f32x4 dprev = {-1.f, -1.f, -1.f, -1.f};
+      float dprev0 = -1.f;  // ROW0: the one register that carries test values
+      // ROW0: both sparse instructions accumulate in place, and rows 4 g4 + 1 .. 3 meet zero A
+      // rows: registers 1-3 are zeroed here, once a tile, and carried from pair to pair with
+      // register 0 re-seeded (nothing reads them)
+      f32x4 dz = {};
       for (int u = 0; u < nu; u += 2) {
         // the wave issues its layer-2 block ahead of waves in their epilogue or append path
         // (kernel only 1.577 -> 1.556 ms: profiles/ncf_scan_pipe_ab.txt); 0 again at the epilogue
@@ -592,8 +651,10 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         // pass_test's four compares, named here too: in program order they then stand among the
         // formation above, and the group barriers below take them into the first eight gaps
         // (pass_test's own fold into these)
-        const uint64_t early = __ballot(!(dprev[0] < 0.f)) | __ballot(!(dprev[1] < 0.f)) |
-                               __ballot(!(dprev[2] < 0.f)) | __ballot(!(dprev[3] < 0.f));
+        // (ROW0: the one compare)
+        const uint64_t early = ROW0 ? __ballot(!(dprev0 < 0.f))
+                                    : __ballot(!(dprev[0] < 0.f)) | __ballot(!(dprev[1] < 0.f)) |
+                                          __ballot(!(dprev[2] < 0.f)) | __ballot(!(dprev[3] < 0.f));
         asm volatile("" ::"s"(early));
 #pragma unroll
         for (int n = 0; n < 2; ++n)
@@ -610,14 +671,27 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
           asm volatile("" : "+v"(xa[n]), "+v"(xb[n]));
         }
         HNM_SGB(0x100, 2)
+        if constexpr (ROW0) {  // 16 packed adds and the one compare
+        HNM_SGB_MFMA_VALU(3) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2)
+        HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2)
+        } else {
         HNM_SGB_MFMA_VALU(3) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(3) HNM_SGB_MFMA_VALU(2)
         HNM_SGB_MFMA_VALU(3) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(3) HNM_SGB_MFMA_VALU(2)
+        }
         HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2)
         HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2) HNM_SGB_MFMA_VALU(2)
+        if constexpr (ROW0) dprev = (f32x4){dprev0, 0.f, 0.f, 0.f};
         pass_test(dprev, u - 2);  // the pair before this one
         __builtin_amdgcn_s_setprio(0);
         // lanes 0-15: (a, c), (a, c + 16), (b, c), (b, c + 16); other lanes' rows are unused
-        f32x4 d = *reinterpret_cast<const f32x4*>(&g7[((u >> 1) * 16 + (lane & 15)) << 2]);
+        // ROW0: lane 32 user + item reads its one seed; rows 4 g4 + 1 .. 3 are unused (dz)
+        f32x4 d;
+        if constexpr (ROW0) {
+          d = dz;
+          d[0] = g7[(u >> 1) * 64 + lane];
+        } else {
+          d = *reinterpret_cast<const f32x4*>(&g7[((u >> 1) * 16 + (lane & 15)) << 2]);
+        }
         pa1 = ldp(u + 2, 1);
         pb1 = ldp(u + 3, 1);
         if constexpr (SPARSE) {
@@ -653,6 +727,8 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
         HNM_SGB(0x008, 1)
         }  // !SPARSE
         dprev = d;  // tested in the next iteration
+        dprev0 = d[0];
+        dz = d;
       }
 #undef HNM_SGB_MFMA_VALU
 #undef HNM_SGB
@@ -672,6 +748,7 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
                         : z;
           }
       }
+      if constexpr (ROW0) dprev = (f32x4){dprev0, 0.f, 0.f, 0.f};
       pass_test(dprev, (nu - 1) & ~1);  // the tile's last pair
     } else {
     f32x4 dprev = {-1.f, -1.f, -1.f, -1.f};
@@ -741,7 +818,10 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
           yb[f] = __builtin_elementwise_min(__builtin_elementwise_max(yb[f], (h8){}), (h8)(_Float16)1.f);
         }
         // lanes 0-15: (a, c), (a, c + 16), (b, c), (b, c + 16); other lanes' rows are unused
-        f32x4 d = *reinterpret_cast<const f32x4*>(&g7[((u >> 1) * 16 + (lane & 15)) << 2]);
+        // (ROW0: lane 32 user + item reads its one seed into d[0]; d[1..3] meet zero A rows)
+        f32x4 d = {};
+        if constexpr (ROW0) d[0] = g7[(u >> 1) * 64 + lane];
+        else d = *reinterpret_cast<const f32x4*>(&g7[((u >> 1) * 16 + (lane & 15)) << 2]);
         if constexpr (DEEP) {
 #pragma unroll
           for (int uu = 0; uu < 2; ++uu)
@@ -773,6 +853,14 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
           const float cua = hnm_readlane_f(cu, ua), cub = hnm_readlane_f(cu, ub);
           const float eua = hnm_readlane_f(eu, ua), eub = hnm_readlane_f(eu, ub);
           const uint64_t vmask = vm32 | (hasb ? vm32 << 32 : 0ull);
+          if constexpr (ROW0) {
+            // every lane stores its one pair: user lane >> 5, item j, whose bound terms it holds
+            if ((vmask >> lane) & 1) {
+              const int64_t o = (u0 + ua + h) * A.ldo + base + j;
+              A.dense[o] = d[0];
+              A.dense2[o] = (h ? eub : eua) + fmaf(h ? cub : cua, dj, bj);
+            }
+          } else
           if (lane < 16) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -786,6 +874,9 @@ __global__ __launch_bounds__(256, DEEP ? 2 : HNM_SCAN_OCC) void ncf16_scan_kerne
           }
         } else if (MODE == SCAN_SAMPLE) {
           const uint64_t vmask = vm32 | (hasb ? vm32 << 32 : 0ull);
+          if constexpr (ROW0) {
+            if ((vmask >> lane) & 1) A.dense[(u0 + ua + h) * A.ldo + base + j] = d[0];  // score - e_i
+          } else
           if (lane < 16) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -839,13 +930,20 @@ void launch_scan(hnm_ctx* ctx, dim3 grid, const ScanArgs& a) {
   else if (ctx->scan_shape && ctx->scan_pipe && MODE == SCAN_THRESH) {
     // HNM_OPT_SCAN_PIPE: the threshold pass of layout 1 with its pair loop pipelined by hand
     // (HNM_OPT_SCAN_SPARSE: every pass of layout 1 with the epilogue on the sparse instruction)
-    if (ctx->scan_sparse)
+    // (HNM_OPT_SCAN_ROW0: every pass with the sparse epilogue, the test values in one register)
+    if (ctx->scan_sparse && ctx->scan_row0)
+      hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, 1, true, true, true>), grid,
+                         dim3(256), 0, ctx->stream, a);
+    else if (ctx->scan_sparse)
       hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, 1, true, true>), grid, dim3(256), 0,
                          ctx->stream, a);
     else
       hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, 1, true>), grid, dim3(256), 0,
                          ctx->stream, a);
-  } else if (ctx->scan_shape && ctx->scan_sparse)
+  } else if (ctx->scan_shape && ctx->scan_sparse && ctx->scan_row0)
+    hipLaunchKernelGGL((ncf16_scan_kernel<MODE, false, 1, false, true, true>), grid, dim3(256), 0,
+                       ctx->stream, a);
+  else if (ctx->scan_shape && ctx->scan_sparse)
     hipLaunchKernelGGL((ncf16_scan_kernel<MODE, false, 1, false, true>), grid, dim3(256), 0,
                        ctx->stream, a);
   else if (ctx->scan_shape)

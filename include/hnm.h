@@ -124,6 +124,16 @@ enum { HNM_OPT_PREFILTER = 1,
  * and parity switch); candidate counts may differ by a test value next to a threshold.  Layout 0
  * and the deep towers' scan ignore it. */
 #define HNM_OPT_SCAN_SPARSE 10
+/* NeuralCF certified top-K, two-layer towers on the 16x16x32 layout with the sparse epilogue
+ * (HNM_OPT_SCAN_SHAPE 1 and HNM_OPT_SCAN_SPARSE 1), every pass of a call alike: the epilogue's A
+ * operand holds wm in rows 0, 4, 8 and 12 (row 4 (2 user + item half)), so the pair's 64 test
+ * values lie in one accumulator register of all 64 lanes, lane 32 user + item, and the threshold
+ * test is one compare whose result is the pass mask (1, default), or in rows 0-3, the values in
+ * four registers of lanes 0-15 and the test four compares (0).  The same products in the same
+ * order: test values, candidate buffers and every returned id and score are bitwise the same (the
+ * A/B and parity switch).  Ignored where either of the two options above is 0 and by the deep
+ * towers' scan. */
+#define HNM_OPT_SCAN_ROW0 11
 hnm_status hnm_ctx_set_option(hnm_ctx* ctx, int option, int64_t value);
 /* Pre-filter counters since the last reset (counted only while HNM_OPT_STATS is 1): out[0]
  * rows scored, out[1] candidates re-scored in fp32, out[2] rows that took the exact fallback

@@ -3,7 +3,8 @@
 // clock warm-up, so scan variants can be compared without the rest of the step.  Both layouts
 // of the two-layer scan are timed, alternating (SHAPE 0: 32x32x16, 1: 16x16x32;
 // HNM_OPT_SCAN_SHAPE), layout 1 with its pair loop pipelined by hand (HNM_OPT_SCAN_PIPE), and that
-// loop with the epilogue on the sparse instruction (HNM_OPT_SCAN_SPARSE) beside it.
+// loop with the epilogue on the sparse instruction (HNM_OPT_SCAN_SPARSE) beside it, and the sparse
+// epilogue with the test values in rows 0-3 and in rows 0, 4, 8, 12 (HNM_OPT_SCAN_ROW0), alternating.
 // Diagnostic build only (the scan unit is included as text: the kernel is private to it;
 // cert_shape comes from ncf_cert.o through ncf_cert_internal.h):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -c tools/scan_ablation.hip -o build/scan_ablation.o
@@ -27,7 +28,7 @@ static T* dev_fill(size_t n, float lo, float hi, unsigned seed) {
   return d;
 }
 
-template <int SHAPE, bool PIPE = false, bool SPARSE = false>
+template <int SHAPE, bool PIPE = false, bool SPARSE = false, bool ROW0 = false>
 static float time_scan(dim3 grid, const ScanArgs& a) {
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0);
@@ -35,7 +36,7 @@ static float time_scan(dim3 grid, const ScanArgs& a) {
   float best = 1e30f;
   for (int rep = 0; rep < 8; ++rep) {
     (void)hipEventRecord(e0);
-    hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, SHAPE, PIPE, SPARSE>), grid, dim3(256), 0, 0, a);
+    hipLaunchKernelGGL((ncf16_scan_kernel<SCAN_THRESH, false, SHAPE, PIPE, SPARSE, ROW0>), grid, dim3(256), 0, 0, a);
     (void)hipEventRecord(e1);
     (void)hipEventSynchronize(e1);
     if (hipGetLastError() != hipSuccess) printf("launch error\n");
@@ -97,6 +98,14 @@ int main() {
     const float ms = pipe ? (sparse ? time_scan<1, true, true>(grid, a) : time_scan<1, true>(grid, a))
                           : (sparse ? time_scan<1, false, true>(grid, a) : time_scan<1>(grid, a));
     printf("ncf16_scan shape 1 pipe %d sparse %d  %7.3f ms\n", pipe, sparse, ms);
+  }
+  // the sparse epilogue's test values in four registers of lanes 0-15 and in one register of all 64
+  // lanes, alternating: the pipelined threshold pass (seven rounds), then the plain loop
+  for (int rep = 0; rep < 20; ++rep) {
+    const int row0 = rep & 1, pipe = rep < 14;
+    const float ms = pipe ? (row0 ? time_scan<1, true, true, true>(grid, a) : time_scan<1, true, true>(grid, a))
+                          : (row0 ? time_scan<1, false, true, true>(grid, a) : time_scan<1, false, true>(grid, a));
+    printf("ncf16_scan shape 1 pipe %d sparse 1 row0 %d  %7.3f ms\n", pipe, row0, ms);
   }
   return 0;
 }
