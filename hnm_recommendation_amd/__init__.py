@@ -4,14 +4,15 @@ Embedding lookup -> all-items scoring (NeuralCF / LightGCN / Wide&Deep / MF) -> 
 the popularity baseline's fit and per-user top-K, and item-based collaborative filtering
 (co-occurrence fit, per-user and per-basket top-K), and implicit-feedback ALS (Gram matrix
 and per-row Cholesky solves: the fit, fold-in of a basket), and the fusion of several models'
-top-K lists into one (an ensemble: reciprocal rank fusion, weighted scores, cascade),
+top-K lists into one (an ensemble: reciprocal rank fusion, weighted scores, cascade), and
+item-attribute nearest neighbours (a dense all-pairs fit: the answer for articles without purchases),
 as hand-written gfx950 HIP kernels behind the C ABI in include/hnm.h (libhnm_mi355x.so),
 exposed through modules that mirror the reference's `src/models` surface.
 """
 from .evaluation import RecommendationMetrics
-from .models import (Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
+from .models import (ContentKNN, Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
                      PopularityBaseline, UserHistory, WeightedItemCF, WideDeep)
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
-           "ItemCF", "WeightedItemCF", "ImplicitALS", "Ensemble", "RecommendationMetrics",
-           "UserHistory"]
+           "ItemCF", "WeightedItemCF", "ContentKNN", "ImplicitALS", "Ensemble",
+           "RecommendationMetrics", "UserHistory"]

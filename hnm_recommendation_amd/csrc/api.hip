@@ -318,6 +318,10 @@ extern "C" hnm_status hnm_ctx_check(hnm_ctx* ctx) {
                     "output rows are NaN)");
       return HNM_EINVAL;
     }
+    if (h & HNM_ERR_CODE_Q) {
+      hnm_set_error("hnm_content_fit_f32: a code weight above 2^20 (it counted as 0)");
+      return HNM_EINVAL;
+    }
   }
   return HNM_OK;
 }

@@ -348,6 +348,7 @@ __device__ __forceinline__ int64_t mask_lower_bound(const int32_t* midx, int64_t
 #define HNM_ERR_OOB 1u
 #define HNM_ERR_MASK_CAP 4u  // hnm_mask_gather_csr: the batch mask exceeded its capacity
 #define HNM_ERR_WEIGHT 8u    // hnm_als_solve_rows_weighted_f32: a negative or non-finite weight
+#define HNM_ERR_CODE_Q 16u   // hnm_content_fit_f32: a code weight above 2^20
 __device__ __forceinline__ void hnm_flag(unsigned* err, unsigned bit) {
   if (err) atomicOr(err, bit);
 }

@@ -37,6 +37,7 @@
 // paragraph is tests/itemcf_oracle.py too.
 #include "hnm_device.h"
 #include "hnm_internal.h"
+#include "itemcf_internal.h"
 
 #include <cfloat>
 #include <cmath>
@@ -59,34 +60,7 @@ constexpr int ICF_DENSE_POOL = 128;       // workspace rows (and workgroups) of 
 constexpr int ICF_GRID_USERS = 4096;
 
 // ------------------------------------------------------------------ shared device pieces
-// Offer one candidate per lane to a single-register wave list (slot s in lane s, K <= 64).
-__device__ __forceinline__ void icf_offer(float& lv, int& li, float sv, int si, bool valid, int K) {
-  const float tv = hnm_readlane_f(lv, K - 1);
-  const int ti = hnm_readlane_i(li, K - 1);
-  uint64_t m = __ballot(valid && hnm_better(sv, si, tv, ti));
-  while (m) {
-    const int l = __builtin_ctzll(m);
-    m &= m - 1;
-    list1_insert(lv, li, hnm_readlane_f(sv, l), hnm_readlane_i(si, l), K);
-  }
-}
-
-// Fold the lists of waves 1..3 of a 256-thread workgroup into wave 0's (mv / mi: 256 slots of
-// LDS).  Every thread calls it; the result is valid in wave 0.
-__device__ __forceinline__ void icf_merge4(float& lv, int& li, float* mv, int* mi, int K) {
-  const int t = threadIdx.x;
-  mv[t] = lv;
-  mi[t] = li;
-  __syncthreads();
-  if (t < 64) {
-    for (int w = 1; w < 4; ++w) {
-      const float cv = mv[w * 64 + t];
-      const int ci = mi[w * 64 + t];
-      icf_offer(lv, li, cv, ci, ci != HNM_SENTINEL_IDX, K);
-    }
-  }
-}
-
+// (icf_offer and icf_merge4, the wave list: itemcf_internal.h)
 __device__ __forceinline__ bool icf_masked(const int32_t* midx, int64_t m0, int64_t m1, int item) {
   const int64_t p = mask_lower_bound(midx, m0, m1, item);
   return p < m1 && midx[p] == item;

@@ -1,0 +1,36 @@
+// The wave-resident top-N list of the neighbour-table fits (itemcf.hip, content.hip): slot s of a
+// row's list lives in lane s of one register pair, (value descending, index ascending) order.
+#pragma once
+#include "hnm_device.h"
+
+namespace {
+
+// Offer one candidate per lane to a single-register wave list (slot s in lane s, K <= 64).
+__device__ __forceinline__ void icf_offer(float& lv, int& li, float sv, int si, bool valid, int K) {
+  const float tv = hnm_readlane_f(lv, K - 1);
+  const int ti = hnm_readlane_i(li, K - 1);
+  uint64_t m = __ballot(valid && hnm_better(sv, si, tv, ti));
+  while (m) {
+    const int l = __builtin_ctzll(m);
+    m &= m - 1;
+    list1_insert(lv, li, hnm_readlane_f(sv, l), hnm_readlane_i(si, l), K);
+  }
+}
+
+// Fold the lists of waves 1..3 of a 256-thread workgroup into wave 0's (mv / mi: 256 slots of
+// LDS).  Every thread calls it; the result is valid in wave 0.
+__device__ __forceinline__ void icf_merge4(float& lv, int& li, float* mv, int* mi, int K) {
+  const int t = threadIdx.x;
+  mv[t] = lv;
+  mi[t] = li;
+  __syncthreads();
+  if (t < 64) {
+    for (int w = 1; w < 4; ++w) {
+      const float cv = mv[w * 64 + t];
+      const int ci = mi[w * 64 + t];
+      icf_offer(lv, li, cv, ci, ci != HNM_SENTINEL_IDX, K);
+    }
+  }
+}
+
+}  // namespace

@@ -5,9 +5,10 @@ from .neural_cf import NeuralCF
 from .popularity import PopularityBaseline
 from .base import UserHistory
 from .item_cf import ItemCF, WeightedItemCF
+from .content_knn import ContentKNN
 from .implicit_als import ImplicitALS
 from .wide_deep import WideDeep
 from .ensemble import Ensemble
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
-           "ItemCF", "WeightedItemCF", "ImplicitALS", "UserHistory", "Ensemble"]
+           "ItemCF", "WeightedItemCF", "ContentKNN", "ImplicitALS", "UserHistory", "Ensemble"]

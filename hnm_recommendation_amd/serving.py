@@ -31,6 +31,9 @@ article-metadata tables (out of scope: SURVEY §2):
 * `Recommender.add_ensemble` -- no reference counterpart: an `Ensemble` of registered models
   under "ensemble" (reciprocal rank fusion, weighted scores or cascade of their top-K lists, fused
   on the GPU); it answers through the same request paths as its members.
+* `Recommender.add_content_knn` -- no reference counterpart: a `ContentKNN` fitted on the
+  catalogue's attribute table under "content_knn": ItemCF's table and answers (users, baskets,
+  back-fill, ensemble member) for articles that have no purchases yet.
 """
 from __future__ import annotations
 
@@ -42,7 +45,7 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import torch
 
-from .models import (Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
+from .models import (ContentKNN, Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
                      PopularityBaseline, WeightedItemCF, WideDeep)
 from .models.base import UserHistory
 
@@ -54,12 +57,13 @@ MAX_NUM_ITEMS = 100
 BASELINE = "popularity_baseline"  # serve.py:273: the name the reference registers it under
 ITEM_CF = "item_cf"
 ALS = "implicit_als"
+CONTENT_KNN = "content_knn"
 ENSEMBLE = "ensemble"
 
 # serve.py:238-248, tested in this order
 _DISPATCH = (("matrix_factorization", MatrixFactorization), ("neural_cf", NeuralCF),
              ("wide_deep", WideDeep), ("lightgcn", LightGCN), (ITEM_CF, ItemCF),
-             (ALS, ImplicitALS))
+             (ALS, ImplicitALS), (CONTENT_KNN, ContentKNN))
 
 
 def load_checkpoint(path: str, device="cpu") -> Dict:
@@ -171,6 +175,22 @@ class Recommender:
         self.add_model(name, model)
         if not self.user_history and self._history_dev is None:
             self._history_dev = model.history
+        return model
+
+    def add_content_knn(self, item_attributes, column_weights=None, weighting: str = "idf",
+                        **kw) -> ContentKNN:
+        """Fit a `ContentKNN` (keywords: num_neighbors, top_k) on the catalogue's attribute table
+        ([num_items, F] integer codes, negative = missing; `column_weights`, `weighting`: see
+        `ContentKNN.fit_attributes`) and register it as "content_knn".  It reads users' rows from
+        the recommender's device history when there is one; without one it still answers baskets
+        (`get_recommendations_for_items(model_name="content_knn")`), and a user request raises."""
+        model = ContentKNN(self.num_users, self.num_items, weighting=weighting, **kw)
+        model = model.to(self.device)
+        model.fit_attributes(item_attributes, column_weights=column_weights)
+        hist = self._device_history()
+        if hist is not None:
+            model.set_history(hist)
+        self.add_model(CONTENT_KNN, model)
         return model
 
     def add_als(self, user_ids, item_ids, weights=None, days_ago=None, time_decay: float = 0.0,

@@ -229,3 +229,36 @@ def filter_dict(user_ids, num_items, per_user=23, seed=3):
         n = int(rng.integers(0, 2 * per_user + 1))
         out[int(u)] = set(int(x) for x in rng.choice(num_items, size=min(n, num_items), replace=False))
     return out
+
+
+# Vocabulary sizes of the default attribute table: eleven columns between 5 and about 300 codes,
+# the range of the categorical columns of the public articles table (product type, graphical
+# appearance, colour group, ..., department).  They are the benchmark tool's shape, not a parity
+# claim: no articles file is read anywhere.
+ATTRIBUTE_VOCAB = (132, 30, 50, 8, 20, 299, 10, 5, 57, 21, 19)
+
+
+def item_attributes(num_items, seed=5, vocab=ATTRIBUTE_VOCAB, zipf=0.9, duplicates=0.3,
+                    missing=0.0):
+    """A categorical attribute table int32 [num_items, len(vocab)]: column f draws codes in
+    [0, vocab[f]) Zipf-like (p ~ rank^-zipf through a fixed permutation, as `interactions` draws
+    items).  A share `duplicates` of the rows are then exact copies of an earlier row (colour
+    variants of one product: what makes ties at the N-th place common in a real catalogue), and a
+    share `missing` of the entries are set to -1 afterwards."""
+    rng = _rng(seed)
+    a = np.empty((num_items, len(vocab)), np.int32)
+    for f, v in enumerate(vocab):
+        p = np.arange(1, v + 1, dtype=np.float64) ** (-zipf)
+        cdf = np.cumsum(p)
+        cdf /= cdf[-1]
+        ranks = np.minimum(np.searchsorted(cdf, rng.random(num_items), side="right"), v - 1)
+        a[:, f] = rng.permutation(v)[ranks]
+    if num_items > 1 and duplicates > 0:
+        rows = np.nonzero(rng.random(num_items) < duplicates)[0]
+        rows = rows[rows > 0]
+        src = (rng.random(len(rows)) * rows).astype(np.int64)      # an earlier row each
+        for r, s in zip(rows, src):                                # in order: copies of copies
+            a[r] = a[s]
+    if missing > 0:
+        a[rng.random(a.shape) < missing] = -1
+    return a

@@ -805,6 +805,43 @@ hnm_status hnm_itemcf_topk_weighted_f32(hnm_ctx* ctx, const int32_t* nbr_idx,
                                         const int64_t* mask_ptr, const int32_t* mask_idx, int k,
                                         float* out_val, int64_t* out_idx);
 
+/* ---- ContentKNN: item-attribute similarity (no reference counterpart) ----------------------
+ * The fit of a neighbour table from the catalogue's categorical attributes instead of purchases:
+ * an item nobody has bought yet still has a row.  The table is hnm_itemcf_fit_f32's (selection,
+ * order, padding), so hnm_itemcf_scores_f32 / hnm_itemcf_topk_f32 serve it unchanged.
+ *
+ * attrs int32[num_items, F], row-major, 1 <= F <= 16: column f holds the item's code in that
+ * column's own vocabulary [0, V_f), V_f = code_ptr[f + 1] - code_ptr[f] (code_ptr int64[F + 1],
+ * ascending from an offset >= 0; device memory like every other pointer).  A negative code is
+ * missing and matches nothing.  A code >= V_f raises the ctx error word (HNM_EOOB from
+ * hnm_ctx_check) and counts as missing; so does every code when code_ptr does not ascend.
+ * code_q uint32[code_ptr[F]]: the fixed-point weight of code v of column f is
+ * code_q[code_ptr[f] + v] <= 2^20; a larger one raises its own bit of the error word (HNM_EINVAL
+ * from hnm_ctx_check; HNM_EOOB is named first when both were seen) and counts as 0.  The weight
+ * belongs to the (column, code) pair: two items that match in a column carry the same weight
+ * there, so S below is symmetric.  With q_if = that weight, or 0 for a missing code,
+ *   n_i = sum_f q_if  (<= 2^24)        item_count[i] = the number of columns with q_if > 0
+ *   S_ij = sum_f [a_if == a_jf and a_if >= 0] * q_if          (i != j, an exact integer)
+ * and for S_ij > 0
+ *   sim[i, j] = (float)( (double)S / sqrt((double)n_i * (double)n_j) )
+ * in float64 with one rounding per operation and no fma (n_i * n_j < 2^48 is exact), rounded
+ * once to float32: hnm_itemcf_fit_f32's rule.  Row i of nbr_idx int32[num_items, N] / nbr_val
+ * f32[num_items, N], 1 <= N <= 64, holds the N largest entries in (float32 sim descending, j
+ * ascending) order, padded with (-1, 0.0f).  An item with n_i = 0 has an empty row and is
+ * nobody's neighbour.  The order is the rounded float32 value's: sims that differ in float64 and
+ * collapse in float32 are ordered by j.  Integers up to the float64 expression: the same bits on
+ * every run, and on every `tile`.
+ *
+ * A dense num_items^2 scan (a wave keeps a few rows' codes in scalar registers and streams the
+ * column items in LDS tiles); the float64 expression is evaluated only for pairs that pass a
+ * conservative fp32 upper bound of sim against the row's current N-th value (csrc/content.hip
+ * argues the bound).  `tile`: column items per LDS tile (0 = default 512; else a multiple of 64
+ * in [64, 512]).  Workspace: 8 F + 8 bytes per item.  No stream sync.  num_items = 0: HNM_OK,
+ * nothing launched.  num_items < 2^31. */
+hnm_status hnm_content_fit_f32(hnm_ctx* ctx, const int32_t* attrs, int64_t num_items, int F,
+                               const int64_t* code_ptr, const uint32_t* code_q, int N, int tile,
+                               int32_t* nbr_idx, float* nbr_val, int64_t* item_count);
+
 /* ---- Fusion of overlapping top-K lists: an ensemble of models (no reference counterpart) ----
  * hnm_topk_merge_f32 merges lists whose items are disjoint.  Here G models each give a list per
  * row, the same item may stand in several of them, and its fused score depends on every list
