@@ -6,13 +6,15 @@ the popularity baseline's fit and per-user top-K, and item-based collaborative f
 and per-row Cholesky solves: the fit, fold-in of a basket), and the fusion of several models'
 top-K lists into one (an ensemble: reciprocal rank fusion, weighted scores, cascade), and
 item-attribute nearest neighbours (a dense all-pairs fit: the answer for articles without purchases),
+and popular lists per user segment (the answer for customers without purchases),
 as hand-written gfx950 HIP kernels behind the C ABI in include/hnm.h (libhnm_mi355x.so),
 exposed through modules that mirror the reference's `src/models` surface.
 """
 from .evaluation import RecommendationMetrics
 from .models import (ContentKNN, Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
-                     PopularityBaseline, UserHistory, WeightedItemCF, WideDeep)
+                     PopularityBaseline, SegmentPopularity, UserHistory, WeightedItemCF, WideDeep,
+                     age_segments)
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
            "ItemCF", "WeightedItemCF", "ContentKNN", "ImplicitALS", "Ensemble",
-           "RecommendationMetrics", "UserHistory"]
+           "RecommendationMetrics", "UserHistory", "SegmentPopularity", "age_segments"]

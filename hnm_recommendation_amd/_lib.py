@@ -161,6 +161,14 @@ _SIGS = {
     # ctx, order, order_val, R, rank, num_items, mask_ptr, mask_idx, B, k, chunk, out_val, out_idx
     "hnm_popularity_topk_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, _p, _p, _i64, C.c_int, C.c_int,
                                        _p, _p]),
+    # ctx, item_ids, user_ids, n, user_segment, num_users, days_ago, day_weight, num_items,
+    # num_segments, num_days, slab, count, pop
+    "hnm_segpop_fit_f64": (_i32, [_p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _i64, _p,
+                                  _p]),
+    # ctx, order, order_val, order_ptr, rank, num_items, num_segments, seg, mask_ptr, mask_idx, B,
+    # k, chunk, out_val, out_idx, out_nseg
+    "hnm_segpop_topk_f32": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _i64, C.c_int,
+                                   C.c_int, _p, _p, _p]),
     # ctx, hist_ptr, hist_idx, num_users, num_items, N, shrink, max_history, window, nbr_idx,
     # nbr_val, item_count
     "hnm_itemcf_fit_f32": (_i32, [_p, _p, _p, _i64, _i64, C.c_int, C.c_double, _i64, C.c_int, _p,

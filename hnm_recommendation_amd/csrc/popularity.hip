@@ -17,13 +17,9 @@
 // first k clear positions by ballot + popcount prefix: O(k + h) per user instead of O(I).
 #include "hnm_device.h"
 #include "hnm_internal.h"
+#include "popularity_internal.h"
 
 namespace {
-
-constexpr size_t POP_TABLE_CAP = (size_t)256 << 20;  // count-table bytes per slab pass
-constexpr int POP_MAX_DAYS = 65536;
-constexpr int POP_FILL_BLOCKS = 2048;
-constexpr int POP_CHUNK_MAX = 8192;  // bits of the LDS rank bitmap (1 KiB per workgroup)
 
 // cnt[(d - d0) * I + item] += 1 for the rows whose day falls in the slab [d0, d1).
 __global__ __launch_bounds__(256) void pop_fill_kernel(const int64_t* __restrict__ item_ids,

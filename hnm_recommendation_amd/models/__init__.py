@@ -3,6 +3,7 @@ from .lightgcn import LightGCN
 from .matrix_factorization import MatrixFactorization
 from .neural_cf import NeuralCF
 from .popularity import PopularityBaseline
+from .segment_popularity import SegmentPopularity, age_segments
 from .base import UserHistory
 from .item_cf import ItemCF, WeightedItemCF
 from .content_knn import ContentKNN
@@ -11,4 +12,5 @@ from .wide_deep import WideDeep
 from .ensemble import Ensemble
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
-           "ItemCF", "WeightedItemCF", "ContentKNN", "ImplicitALS", "UserHistory", "Ensemble"]
+           "ItemCF", "WeightedItemCF", "ContentKNN", "ImplicitALS", "UserHistory", "Ensemble",
+           "SegmentPopularity", "age_segments"]

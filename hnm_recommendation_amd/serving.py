@@ -34,6 +34,11 @@ article-metadata tables (out of scope: SURVEY §2):
 * `Recommender.add_content_knn` -- no reference counterpart: a `ContentKNN` fitted on the
   catalogue's attribute table under "content_knn": ItemCF's table and answers (users, baskets,
   back-fill, ensemble member) for articles that have no purchases yet.
+* `Recommender.add_segment_popularity` -- no reference counterpart (its analysis script names the
+  strategy): a `SegmentPopularity` fitted on the transactions and the users' segments under
+  "segment_popularity".  With `cold_start="segment"` an unknown user is answered by it from the
+  request's `segment` (the popular list of that age / membership group, continued from the
+  global list); known users reach it by name or through an ensemble.
 """
 from __future__ import annotations
 
@@ -46,7 +51,7 @@ from typing import Dict, List, Optional, Sequence, Union
 import torch
 
 from .models import (ContentKNN, Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
-                     PopularityBaseline, WeightedItemCF, WideDeep)
+                     PopularityBaseline, SegmentPopularity, WeightedItemCF, WideDeep)
 from .models.base import UserHistory
 
 logger = logging.getLogger(__name__)
@@ -59,6 +64,7 @@ ITEM_CF = "item_cf"
 ALS = "implicit_als"
 CONTENT_KNN = "content_knn"
 ENSEMBLE = "ensemble"
+SEGMENT_POP = "segment_popularity"
 
 # serve.py:238-248, tested in this order
 _DISPATCH = (("matrix_factorization", MatrixFactorization), ("neural_cf", NeuralCF),
@@ -109,8 +115,10 @@ class Recommender:
     purchase history, `:166-168`); customer_index: optional {customer_id str: user_idx}
     (the encoder lookup, `:294-300`); article_ids: optional sequence item_idx -> article id.
     cold_start: what an unknown user gets -- "error" (the reference: ValueError / an error
-    entry) or "popularity" (opt-in: the unfiltered popular list of the registered
-    "popularity_baseline", under that model name).
+    entry), "popularity" (opt-in: the unfiltered popular list of the registered
+    "popularity_baseline", under that model name) or "segment" (opt-in: the unfiltered list of
+    the registered "segment_popularity" for the request's `segment`, under that model name; a
+    request without a segment gets that model's global list).
     """
 
     def __init__(self, num_users: int, num_items: int, models: Optional[Dict] = None,
@@ -119,8 +127,8 @@ class Recommender:
                  customer_index: Optional[Dict[str, int]] = None,
                  article_ids: Optional[Sequence] = None, device="cuda",
                  cold_start: str = "error"):
-        if cold_start not in ("error", "popularity"):
-            raise ValueError('cold_start must be "error" or "popularity"')
+        if cold_start not in ("error", "popularity", "segment"):
+            raise ValueError('cold_start must be "error", "popularity" or "segment"')
         self.cold_start = cold_start
         self.num_users = num_users
         self.num_items = num_items
@@ -150,6 +158,22 @@ class Recommender:
                                    time_decay=time_decay).to(self.device)
         model.fit_interactions(item_ids, days_ago=days_ago, window_days=window_days)
         self.add_model(BASELINE, model)
+        return model
+
+    def add_segment_popularity(self, item_ids, user_ids, user_segments, n_segments: int,
+                               days_ago=None, time_decay: float = 0.0,
+                               window_days: Optional[int] = None,
+                               min_count: int = 1) -> SegmentPopularity:
+        """Fit a `SegmentPopularity` on the transactions and `user_segments[user]` (in
+        [0, n_segments), negative = unknown; e.g. `age_segments` of the customers table) and
+        register it as "segment_popularity": the answer `cold_start="segment"` gives an unknown
+        user, and a recall source for known users (by name, or as an `add_ensemble` member)."""
+        model = SegmentPopularity(self.num_items, n_segments,
+                                  k=min(MAX_NUM_ITEMS, self.num_items), time_decay=time_decay,
+                                  min_count=min_count).to(self.device)
+        model.fit_interactions(item_ids, user_ids, user_segments, days_ago=days_ago,
+                               window_days=window_days)
+        self.add_model(SEGMENT_POP, model)
         return model
 
     def add_item_cf(self, user_ids, item_ids, weights=None, days_ago=None,
@@ -284,6 +308,39 @@ class Recommender:
                              "(add_popularity_baseline)")
         return self.models[BASELINE]
 
+    def _request_segments(self, segments, n: int):
+        """The `segment` / `segments` keyword of a request with n entries: None unless
+        cold_start="segment"; then one int per entry (None -> -1), checked on the host against
+        the registered "segment_popularity" -- ValueError before any launch."""
+        if self.cold_start != "segment":
+            if segments is not None and any(s is not None for s in segments):
+                raise ValueError('a request segment needs cold_start="segment"')
+            return None
+        if SEGMENT_POP not in self.models:
+            raise ValueError('cold_start="segment" needs a registered "segment_popularity" '
+                             "(add_segment_popularity)")
+        segs = [None] * n if segments is None else list(segments)
+        if len(segs) != n:
+            raise ValueError("segments must have one entry per user id")
+        S = self.models[SEGMENT_POP].num_segments
+        out = []
+        for s in segs:
+            if s is not None and (isinstance(s, bool) or not isinstance(s, int)
+                                  or not -1 <= s < S):
+                raise ValueError(f"segment must be None or an integer in [-1, {S}), got {s!r}")
+            out.append(-1 if s is None else s)
+        return out
+
+    def _score_segments(self, segs: List[int], num_items: int):
+        """Unknown users: one `SegmentPopularity.recommend_for_segments` call for all of them,
+        unfiltered (they have no history)."""
+        self._check_num_items(num_items)
+        with torch.no_grad():
+            vals, items = self.models[SEGMENT_POP].recommend_for_segments(segs, k=num_items)
+        vals, items = vals.cpu().tolist(), items.cpu().tolist()
+        self._trim(vals, items)
+        return vals, items
+
     def _resolve_model(self, model_name: str):
         if model_name == "best":
             model_name = self._get_best_model()
@@ -408,12 +465,18 @@ class Recommender:
 
     def get_recommendations(self, user_id: Union[int, str], model_name: str = "best",
                             num_items: int = 12, filter_purchased: bool = True,
-                            include_scores: bool = False) -> Dict:
+                            include_scores: bool = False, segment: Optional[int] = None) -> Dict:
         """`serve.py:305-371` (ValueError for an unknown user or model; with
-        cold_start="popularity" an unknown user gets the unfiltered popular list)."""
+        cold_start="popularity" an unknown user gets the unfiltered popular list, with
+        cold_start="segment" the list of the request's `segment` -- None or -1: the global one
+        -- from "segment_popularity"; a known user's `segment` is not read)."""
+        segs = self._request_segments(None if segment is None else [segment], 1)
         cold = self._cold_start_model() if self.cold_start == "popularity" else None
         uidx = self.get_user_idx(user_id)
         if uidx is None:
+            if segs is not None:
+                vals, items = self._score_segments(segs, num_items)
+                return self._result(user_id, SEGMENT_POP, vals[0], items[0], include_scores)
             if cold is not None:
                 vals, items = self._score_batch(cold, [0], num_items, False)
                 return self._result(user_id, BASELINE, vals[0], items[0], include_scores)
@@ -425,16 +488,22 @@ class Recommender:
     def get_batch_recommendations(self, user_ids: List[Union[int, str]],
                                   model_name: str = "best", num_items: int = 12,
                                   filter_purchased: bool = True,
-                                  include_scores: bool = False) -> List[Dict]:
+                                  include_scores: bool = False,
+                                  segments: Optional[Sequence[Optional[int]]] = None
+                                  ) -> List[Dict]:
         """`serve.py:373-413`, batched: one fused scoring + mask + top-k call for all
         known users; unknown users get {'user_id', 'error'} in their slot -- or, with
-        cold_start="popularity", the unfiltered popular list (one more call for all of them)."""
+        cold_start="popularity", the unfiltered popular list (one more call for all of them),
+        or, with cold_start="segment", the list of their entry of `segments` (one per user id,
+        None or -1: the global list) from "segment_popularity": one more call for all of them,
+        whatever their segments."""
+        segs = self._request_segments(segments, len(user_ids))
         cold = self._cold_start_model() if self.cold_start == "popularity" else None
         name, model = self._resolve_model(model_name)
         idx, slots, results, cold_slots = [], [], [], []
         for j, uid in enumerate(user_ids):
             u = self.get_user_idx(uid)
-            if u is None and cold is not None:
+            if u is None and (cold is not None or segs is not None):
                 results.append(None)
                 cold_slots.append(j)
             elif u is None:
@@ -449,7 +518,12 @@ class Recommender:
             vals, items = self._score_batch(model, idx, num_items, filter_purchased)
             for r, j in enumerate(slots):
                 results[j] = self._result(user_ids[j], name, vals[r], items[r], include_scores)
-        if cold_slots:  # the same list for every unknown user: user ids play no part unfiltered
+        if cold_slots and segs is not None:
+            vals, items = self._score_segments([segs[j] for j in cold_slots], num_items)
+            for r, j in enumerate(cold_slots):
+                results[j] = self._result(user_ids[j], SEGMENT_POP, vals[r], items[r],
+                                          include_scores)
+        elif cold_slots:  # the same list for every unknown user: user ids play no part unfiltered
             vals, items = self._score_batch(cold, [0], num_items, False)
             for j in cold_slots:
                 results[j] = self._result(user_ids[j], BASELINE, vals[0], items[0], include_scores)

@@ -711,6 +711,48 @@ hnm_status hnm_popularity_topk_f32(hnm_ctx* ctx, const int64_t* order, const flo
                                    const int64_t* mask_ptr, const int32_t* mask_idx, int64_t B,
                                    int k, int chunk, float* out_val, int64_t* out_idx);
 
+/* ---- SegmentPopularity: popular lists per user segment (no reference module; the reference's
+ * analysis names the strategy: "Demographics -> popular items in age/gender group") ---------
+ * Fit: hnm_popularity_fit_f64 with one count table per segment.  item_ids / user_ids int64[n];
+ * user_segment int32[num_users]: a user's segment in [0, num_segments), negative = unknown;
+ * days_ago, day_weight, num_days, slab: as hnm_popularity_fit_f64.  S = num_segments >= 1
+ * (else HNM_EINVAL).  count int64 / pop f64 are [S + 1, num_items]; row S is the global row.
+ * A transaction increments row S and, when s = user_segment[user] >= 0, row s; per row
+ *   count[s, i] = sum_d cnt[d, s, i]
+ *   pop[s, i]   = ((0 + cnt[0,s,i] * w[0]) + cnt[1,s,i] * w[1]) + ...
+ * in ascending d, each product and each add rounded to float64 once (no fma): the same bits on
+ * every run and for every slab, and row S is bitwise hnm_popularity_fit_f64's result.  An item
+ * outside [0, num_items), a user outside [0, num_users) or a segment >= S raises the ctx error
+ * word (HNM_EOOB from hnm_ctx_check), and that transaction is skipped entirely.  The counts sit
+ * in an int32 [slab, S + 1, num_items] table in the ctx workspace; slab = 0 picks the days per
+ * pass from the 256 MiB table cap.  One day's table above the cap, or num_days > 65,536:
+ * HNM_EUNSUPPORTED. */
+hnm_status hnm_segpop_fit_f64(hnm_ctx* ctx, const int64_t* item_ids, const int64_t* user_ids,
+                              int64_t n, const int32_t* user_segment, int64_t num_users,
+                              const int32_t* days_ago, const double* day_weight,
+                              int64_t num_items, int64_t num_segments, int64_t num_days,
+                              int64_t slab, int64_t* count, double* pop);
+/* Per-row top-K: a segment's list, continued from the global one.  The S + 1 orders are
+ * concatenated in order int64 / order_val f32 at the device offsets order_ptr int64[S + 2]
+ * (order S = the global one); rank int32[S + 1, num_items]: position in each order, -1 = not in
+ * it.  seg int32[B]: the row's segment, negative = none (NULL: none for every row); seg >= S
+ * raises the error word and the row is answered as one without a segment.  mask_ptr / mask_idx,
+ * k, chunk: as hnm_popularity_topk_f32.  With hist = row b of the mask and s = seg[b]:
+ *   seg_part = [x for x in order[s] if x not in hist][:k]                  (empty when s < 0)
+ *   rest     = [x for x in order[S] if x not in hist and x not in seg_part][:k - len(seg_part)]
+ * row b of out_val / out_idx [B, k] = seg_part + rest, then (-inf, -1); out_nseg[b] (int32, may
+ * be NULL) = len(seg_part).  Each entry carries the score of the list it came from: the
+ * segment's popularity before position out_nseg[b], the global popularity from there on, so the
+ * scores of a row are NOT monotone across that seam (each part is).  With every row at a
+ * negative segment the result is bitwise hnm_popularity_topk_f32's over order S.  One wave per
+ * row, two phases over windows min(R, k + h_b) of the two orders; phase 2 also marks what phase
+ * 1 emitted.  order == NULL: every order is empty.  k = 0: out_nseg = 0, nothing launched. */
+hnm_status hnm_segpop_topk_f32(hnm_ctx* ctx, const int64_t* order, const float* order_val,
+                               const int64_t* order_ptr, const int32_t* rank, int64_t num_items,
+                               int64_t num_segments, const int32_t* seg, const int64_t* mask_ptr,
+                               const int32_t* mask_idx, int64_t B, int k, int chunk,
+                               float* out_val, int64_t* out_idx, int32_t* out_nseg);
+
 /* ---- ItemCF: item-based collaborative filtering (no reference counterpart) ---------------
  * Fit.  hist_ptr int64[num_users + 1] / hist_idx int32: the de-duplicated user -> item CSR
  * (rows ascending and unique: UserHistory's layout).  A user with more than max_history items
