@@ -7,14 +7,16 @@ and per-row Cholesky solves: the fit, fold-in of a basket), and the fusion of se
 top-K lists into one (an ensemble: reciprocal rank fusion, weighted scores, cascade), and
 item-attribute nearest neighbours (a dense all-pairs fit: the answer for articles without purchases),
 and popular lists per user segment (the answer for customers without purchases),
+and two-stage serving (the recall models' candidates merged per user and re-scored by a neural
+ranker),
 as hand-written gfx950 HIP kernels behind the C ABI in include/hnm.h (libhnm_mi355x.so),
 exposed through modules that mirror the reference's `src/models` surface.
 """
 from .evaluation import RecommendationMetrics
 from .models import (ContentKNN, Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
-                     PopularityBaseline, SegmentPopularity, UserHistory, WeightedItemCF, WideDeep,
-                     age_segments)
+                     PopularityBaseline, Reranker, SegmentPopularity, UserHistory, WeightedItemCF,
+                     WideDeep, age_segments)
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
-           "ItemCF", "WeightedItemCF", "ContentKNN", "ImplicitALS", "Ensemble",
+           "ItemCF", "WeightedItemCF", "ContentKNN", "ImplicitALS", "Ensemble", "Reranker",
            "RecommendationMetrics", "UserHistory", "SegmentPopularity", "age_segments"]

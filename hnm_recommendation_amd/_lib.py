@@ -193,6 +193,17 @@ _SIGS = {
     # mask_idx, k, out_val, out_idx
     "hnm_fuse_topk_f32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i64, C.c_int, C.c_int, _p, _i64,
                                  _p, _p, C.c_int, _p, _p]),
+    # ctx, list_val (may be NULL), list_idx, B, G, gstride, bstride, kc, num_items, out_cand, ldc,
+    # out_n
+    "hnm_cand_union_i32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i64, C.c_int, _i64, _p, _i64,
+                                  _p]),
+    # ctx, scores, cand, ldc, cand_n, B, k, out_val, out_idx
+    "hnm_cand_topk_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, C.c_int, _p, _p]),
+    # ctx, w, user_ids, B, user_features, cand, ldc, cand_n, k, out_val, out_idx, out_scores,
+    # itf, item_features, ldf
+    "hnm_widedeep_cand_topk_ex_f32": (_i32, [_p, C.POINTER(WideDeepWeights), _p, _i64, _p, _p,
+                                             _i64, _p, C.c_int, _p, _p, _p,
+                                             C.POINTER(WideDeepItemFeatures), _p, _i64]),
     # ctx, tab, rows, ld, d, out [d, d]
     "hnm_als_gram_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p]),
     # ctx, ptr, idx, n_rows, tab, tab_rows, ld, d, gram, alpha, reg, row_ids, B, out, ldo

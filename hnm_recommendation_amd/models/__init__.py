@@ -10,7 +10,8 @@ from .content_knn import ContentKNN
 from .implicit_als import ImplicitALS
 from .wide_deep import WideDeep
 from .ensemble import Ensemble
+from .reranker import Reranker
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
            "ItemCF", "WeightedItemCF", "ContentKNN", "ImplicitALS", "UserHistory", "Ensemble",
-           "SegmentPopularity", "age_segments"]
+           "SegmentPopularity", "age_segments", "Reranker"]

@@ -31,6 +31,9 @@ article-metadata tables (out of scope: SURVEY §2):
 * `Recommender.add_ensemble` -- no reference counterpart: an `Ensemble` of registered models
   under "ensemble" (reciprocal rank fusion, weighted scores or cascade of their top-K lists, fused
   on the GPU); it answers through the same request paths as its members.
+* `Recommender.add_reranker` -- no reference counterpart (its analysis script names the
+  architecture): a `Reranker` of registered models under "reranker": the sources' candidates
+  merged per user and re-scored by a registered neural ranker, through the same request paths.
 * `Recommender.add_content_knn` -- no reference counterpart: a `ContentKNN` fitted on the
   catalogue's attribute table under "content_knn": ItemCF's table and answers (users, baskets,
   back-fill, ensemble member) for articles that have no purchases yet.
@@ -51,7 +54,7 @@ from typing import Dict, List, Optional, Sequence, Union
 import torch
 
 from .models import (ContentKNN, Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
-                     PopularityBaseline, SegmentPopularity, WeightedItemCF, WideDeep)
+                     PopularityBaseline, Reranker, SegmentPopularity, WeightedItemCF, WideDeep)
 from .models.base import UserHistory
 
 logger = logging.getLogger(__name__)
@@ -64,6 +67,7 @@ ITEM_CF = "item_cf"
 ALS = "implicit_als"
 CONTENT_KNN = "content_knn"
 ENSEMBLE = "ensemble"
+RERANKER = "reranker"
 SEGMENT_POP = "segment_popularity"
 
 # serve.py:238-248, tested in this order
@@ -242,6 +246,23 @@ class Recommender:
         if unknown:
             raise ValueError(f"models {unknown} are not available")
         model = Ensemble([(n, self.models[n]) for n in names], weights=weights, mode=mode, **kw)
+        self.add_model(name, model)
+        return model
+
+    def add_reranker(self, ranker_name: str, source_names, name: str = RERANKER,
+                     **kw) -> Reranker:
+        """Build a `Reranker` (keywords: depth, top_k) from registered models -- the ranker
+        `ranker_name` over the candidates of `source_names`, in that order -- and register it
+        under `name`; ValueError for a name that is not registered.  It carries no metrics, so
+        `"best"` resolves as before.  Requests go through the existing paths: the history filter
+        reaches the sources, and rows that run out of candidates are back-filled from the
+        popularity baseline when a source's are (`back_fill_short_rows`).  It answers users
+        only: a basket request names it a model that cannot answer from items."""
+        names = list(source_names)
+        unknown = [n for n in [ranker_name, *names] if n not in self.models]
+        if unknown:
+            raise ValueError(f"models {unknown} are not available")
+        model = Reranker(self.models[ranker_name], [(n, self.models[n]) for n in names], **kw)
         self.add_model(name, model)
         return model
 

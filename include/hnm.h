@@ -932,6 +932,73 @@ hnm_status hnm_fuse_topk_f32(hnm_ctx* ctx, const float* list_val, const int64_t*
                              const int64_t* mask_ptr, const int32_t* mask_idx, int k,
                              float* out_val, int64_t* out_idx);
 
+/* ---- Two-stage serving: candidate rows for a ranker (no reference counterpart; the reference's
+ * design note asks for "Stage 1: candidate generation, Stage 2: ranking") --------------------
+ * Candidate union.  G recall sources each give a list per row; the ranker wants every item of a
+ * row once.
+ *
+ * Input.  list_val / list_idx, B, G, gstride, bstride, kc: hnm_fuse_topk_f32's layout, and its
+ * definition of an EMPTY entry: idx < 0, or list_val given (it may be NULL) and the value not
+ * finite.  An entry with idx >= num_items raises the ctx error word (HNM_EOOB from
+ * hnm_ctx_check) and is skipped like an empty one.  An item may stand in several lists of a row,
+ * and more than once in one list.
+ *
+ * Output.  Row b of out_cand int32[B, ldc] holds the distinct non-empty item ids of the row's G
+ * lists in ASCENDING order, out_n[b] of them; positions out_n[b] .. ldc hold -1.
+ * ldc >= G * kc (else HNM_EINVAL).
+ *
+ * Limits: 1 <= G <= 16, 1 <= kc <= 512, G * kc <= 2,048; anything outside is HNM_EUNSUPPORTED
+ * (nothing is written).  B = 0: HNM_OK, nothing launched.  One wave per row: the ids sorted in
+ * LDS by a bitonic network (at most 8 KiB a wave), then compacted with ballot + popcount; no
+ * workspace, no atomics: the same bits on every run.  No stream sync. */
+hnm_status hnm_cand_union_i32(hnm_ctx* ctx, const float* list_val, const int64_t* list_idx,
+                              int64_t B, int64_t G, int64_t gstride, int64_t bstride, int kc,
+                              int64_t num_items, int32_t* out_cand, int64_t ldc, int32_t* out_n);
+
+/* Selection from scored candidate rows.  Row b considers entries j < cand_n[b] (clamped to
+ * [0, ldc]) of scores f32[B, ldc] / cand int32[B, ldc]; an entry with cand < 0, or whose score is
+ * NaN or -inf, is dropped.  Row b of out_val / out_idx [B, k] holds the best k of the rest in
+ * (score descending, item id ascending) order -- the library's total order -- and (-inf, -1)
+ * past the last one.  The candidates of a row must be distinct; if they are not, that row's
+ * result is unspecified, and nothing outside the row's outputs is written.  1 <= k <= 128
+ * (else HNM_EUNSUPPORTED, nothing written).  B = 0: HNM_OK.  One wave per row; no workspace,
+ * no stream sync. */
+hnm_status hnm_cand_topk_f32(hnm_ctx* ctx, const float* scores, const int32_t* cand, int64_t ldc,
+                             const int32_t* cand_n, int64_t B, int k, float* out_val,
+                             int64_t* out_idx);
+
+/* Wide&Deep over candidate rows: score and select in one launch.  w, user_ids, user_features,
+ * itf, item_features, ldf: as hnm_widedeep_topk_ex_f32, and the same per-call preparation
+ * (folded weights, the layer-1 tables of the batch rows and of the WHOLE catalogue, the
+ * item-feature fold): the catalogue's layer-1 table is rebuilt on every call, as in every
+ * Wide&Deep entry.  cand int32[B, ldc] / cand_n int32[B]: row b's candidates are entries
+ * j < cand_n[b] (clamped to [0, ldc]); hnm_cand_union_i32's output.
+ *
+ * The score of (b, item) is BITWISE row b, column item of hnm_widedeep_scores_ex_f32: the same
+ * device function on the same operands in the same order.  A candidate < 0 is skipped; one
+ * >= w->num_items raises the ctx error word (HNM_EOOB from hnm_ctx_check) and is skipped.
+ * Out-of-range user_ids behave as in hnm_widedeep_topk_ex_f32.
+ *
+ * Output.  Row b of out_val / out_idx [B, k]: the row's candidates whose score is neither NaN
+ * nor -inf, best k in (score descending, item ascending) order, (-inf, -1) past the last one.
+ * out_scores f32[B, ldc] (may be NULL): the score of cand[b, j], -inf for skipped candidates
+ * and for positions cand_n[b] .. ldc.  k = 0 with out_scores: only the scores are written
+ * (out_val / out_idx may be NULL); k = 0 without: HNM_EINVAL.  The candidates of a row must be
+ * distinct; if they are not, that row's selection is unspecified, and nothing outside that
+ * row's outputs is written.  There is no mask: the sources of the candidates applied it.
+ *
+ * Limits: 0 <= k <= 64, ldc <= 2,048, and the tower shapes of hnm_widedeep_topk_ex_f32; else
+ * HNM_EUNSUPPORTED (nothing is written).  B = 0: HNM_OK.  One wave per user, walking its list in
+ * tiles of 32.  No stream sync.  hnm_ctx_enable_timing (scoring class) times the candidate
+ * kernel alone, without the preparation. */
+hnm_status hnm_widedeep_cand_topk_ex_f32(hnm_ctx* ctx, const hnm_widedeep_weights* w,
+                                         const int64_t* user_ids, int64_t B,
+                                         const float* user_features, const int32_t* cand,
+                                         int64_t ldc, const int32_t* cand_n, int k,
+                                         float* out_val, int64_t* out_idx, float* out_scores,
+                                         const hnm_widedeep_item_features* itf,
+                                         const float* item_features, int64_t ldf);
+
 /* ---- ImplicitALS: alternating least squares for implicit feedback (Hu, Koren & Volinsky
  * 2008; no reference counterpart) ----------------------------------------------------------
  * Gram matrix.  out f32[d, d] (contiguous) = tab^T tab over the first `rows` rows of tab (row
