@@ -9,14 +9,16 @@ item-attribute nearest neighbours (a dense all-pairs fit: the answer for article
 and popular lists per user segment (the answer for customers without purchases),
 and two-stage serving (the recall models' candidates merged per user and re-scored by a neural
 ranker),
+and directed next-purchase transitions (a counting fit over the time-ordered purchase sequences),
 as hand-written gfx950 HIP kernels behind the C ABI in include/hnm.h (libhnm_mi355x.so),
 exposed through modules that mirror the reference's `src/models` surface.
 """
 from .evaluation import RecommendationMetrics
 from .models import (ContentKNN, Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
-                     PopularityBaseline, Reranker, SegmentPopularity, UserHistory, WeightedItemCF,
-                     WideDeep, age_segments)
+                     PopularityBaseline, Reranker, SegmentPopularity, SequentialCF, UserHistory,
+                     UserSequence, WeightedItemCF, WideDeep, age_segments)
 
 __all__ = ["NeuralCF", "LightGCN", "WideDeep", "MatrixFactorization", "PopularityBaseline",
            "ItemCF", "WeightedItemCF", "ContentKNN", "ImplicitALS", "Ensemble", "Reranker",
-           "RecommendationMetrics", "UserHistory", "SegmentPopularity", "age_segments"]
+           "RecommendationMetrics", "UserHistory", "SegmentPopularity", "age_segments",
+           "SequentialCF", "UserSequence"]

@@ -189,6 +189,10 @@ _SIGS = {
                                             _p, _p, C.c_int, _p, _p]),
     # ctx, attrs, num_items, F, code_ptr, code_q, N, tile, nbr_idx, nbr_val, item_count
     "hnm_content_fit_f32": (_i32, [_p, _p, _i64, C.c_int, _p, _p, C.c_int, C.c_int, _p, _p, _p]),
+    # ctx, seq_ptr, seq_item, seq_day, num_users, num_items, N, shrink, max_history, max_gap,
+    # gap_q, repeat_buys, window, nbr_idx, nbr_val, item_count
+    "hnm_seqcf_fit_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, C.c_int, C.c_double, _i64, C.c_int,
+                                 _p, C.c_int, C.c_int, _p, _p, _p]),
     # ctx, list_val, list_idx, B, G, gstride, bstride, kc, mode, coef, num_items, mask_ptr,
     # mask_idx, k, out_val, out_idx
     "hnm_fuse_topk_f32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i64, C.c_int, C.c_int, _p, _i64,

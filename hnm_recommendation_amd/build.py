@@ -19,7 +19,7 @@ SOURCES = ["api.hip", "score.hip", "dot_cert.hip", "ncf.hip", "ncf_cert.hip", "n
            "ncf_cert_scan.hip", "ncf_cert_rescore.hip", "ncf_deep.hip", "graph.hip", "graph_csr.hip",
            "graph_plan.hip", "widedeep.hip",
            "widedeep_cert.hip", "widedeep_rescore.hip", "widedeep_features.hip", "eval.hip", "topk_sort.hip", "collective.hip",
-           "popularity.hip", "segpop.hip", "itemcf.hip", "content.hip", "als.hip", "als_cg.hip", "fuse.hip",
+           "popularity.hip", "segpop.hip", "itemcf.hip", "content.hip", "seqcf.hip", "als.hip", "als_cg.hip", "fuse.hip",
            "rerank.hip", "widedeep_cand.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",

@@ -231,37 +231,7 @@ __global__ __launch_bounds__(256) void icf_transpose_kernel(
   }
 }
 
-// One workgroup: tptr = exclusive scan of cnt (tptr[I] = total), cursor = tptr[0, I),
-// item_count = cnt as int64.
-__global__ __launch_bounds__(1024) void icf_scan_kernel(const int* __restrict__ cnt, int64_t I,
-                                                        int* __restrict__ tptr,
-                                                        int* __restrict__ cursor,
-                                                        int64_t* __restrict__ item_count) {
-  __shared__ int part[1024];
-  const int t = threadIdx.x;
-  const int64_t per = hnm_cdiv(I, 1024);
-  const int64_t b = std::min<int64_t>(I, t * per), e = std::min<int64_t>(I, b + per);
-  int s = 0;
-  for (int64_t x = b; x < e; ++x) s += cnt[x];
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int base = part[t] - s;
-  for (int64_t x = b; x < e; ++x) {
-    const int c = cnt[x];
-    tptr[x] = base;
-    cursor[x] = base;
-    item_count[x] = c;
-    base += c;
-  }
-  if (t == 1023) tptr[I] = part[1023];
-}
-
+// (icf_scan_kernel, the exclusive scan of the transpose: itemcf_internal.h)
 __device__ __forceinline__ float icf_sim(int c, int ni, int nj, double shrink) {
 #pragma clang fp contract(off)
   const double prod = (double)ni * (double)nj;

@@ -16,6 +16,7 @@ import torch.nn as nn
 from .. import _lib
 from .history import (HistoryModel, UserHistory, _history_arrays, basket_csr,  # noqa: F401
                       filter_csr, interaction_weights, interactions_history)
+from .sequence import UserSequence  # noqa: F401
 
 
 class RecModule(nn.Module):

@@ -42,6 +42,10 @@ article-metadata tables (out of scope: SURVEY §2):
   "segment_popularity".  With `cold_start="segment"` an unknown user is answered by it from the
   request's `segment` (the popular list of that age / membership group, continued from the
   global list); known users reach it by name or through an ensemble.
+* `Recommender.add_sequential_cf` -- no reference counterpart (its analysis script names the
+  "temporal" member): a `SequentialCF` fitted on the transactions and their dates under
+  "sequential_cf": ItemCF's table and answers (users, weighted baskets, back-fill, ensemble member,
+  reranker source), with rows that hold what was bought AFTER an item.
 """
 from __future__ import annotations
 
@@ -54,7 +58,8 @@ from typing import Dict, List, Optional, Sequence, Union
 import torch
 
 from .models import (ContentKNN, Ensemble, ImplicitALS, ItemCF, LightGCN, MatrixFactorization, NeuralCF,
-                     PopularityBaseline, Reranker, SegmentPopularity, WeightedItemCF, WideDeep)
+                     PopularityBaseline, Reranker, SegmentPopularity, SequentialCF, WeightedItemCF,
+                     WideDeep)
 from .models.base import UserHistory
 
 logger = logging.getLogger(__name__)
@@ -69,11 +74,12 @@ CONTENT_KNN = "content_knn"
 ENSEMBLE = "ensemble"
 RERANKER = "reranker"
 SEGMENT_POP = "segment_popularity"
+SEQ_CF = "sequential_cf"
 
 # serve.py:238-248, tested in this order
 _DISPATCH = (("matrix_factorization", MatrixFactorization), ("neural_cf", NeuralCF),
              ("wide_deep", WideDeep), ("lightgcn", LightGCN), (ITEM_CF, ItemCF),
-             (ALS, ImplicitALS), (CONTENT_KNN, ContentKNN))
+             (ALS, ImplicitALS), (CONTENT_KNN, ContentKNN), (SEQ_CF, SequentialCF))
 
 
 def load_checkpoint(path: str, device="cpu") -> Dict:
@@ -220,6 +226,17 @@ class Recommender:
             model.set_history(hist)
         self.add_model(CONTENT_KNN, model)
         return model
+
+    def add_sequential_cf(self, user_ids, item_ids, days_ago, weights=None,
+                          recency_decay: float = 0.0, **kw) -> SequentialCF:
+        """Fit a `SequentialCF` (keywords: num_neighbors, shrink, max_history, max_gap, gap_decay,
+        repeat_buys, top_k) on the transactions' (user, item, days_ago) triples and register it as
+        "sequential_cf".  `weights` / `recency_decay` shape the history a user is answered from,
+        as in `SequentialCF.fit_interactions`.  Its history becomes the recommender's device
+        history when the recommender has none."""
+        return self._add_fitted(SEQ_CF, SequentialCF(self.num_users, self.num_items, **kw),
+                                user_ids, item_ids, days_ago=days_ago, weights=weights,
+                                recency_decay=recency_decay)
 
     def add_als(self, user_ids, item_ids, weights=None, days_ago=None, time_decay: float = 0.0,
                 solver: str = "cholesky", cg_steps: int = 3, **kw) -> ImplicitALS:

@@ -884,6 +884,56 @@ hnm_status hnm_content_fit_f32(hnm_ctx* ctx, const int32_t* attrs, int64_t num_i
                                const int64_t* code_ptr, const uint32_t* code_q, int N, int tile,
                                int32_t* nbr_idx, float* nbr_val, int64_t* item_count);
 
+/* ---- SequentialCF: directed next-purchase transitions (no reference counterpart) ------------
+ * The fit of a neighbour table from the ORDER of purchases: row a holds what customers bought in
+ * the days AFTER a.  The table is hnm_itemcf_fit_f32's (selection, order, padding), and row a
+ * -> b is the direction hnm_itemcf_scores_f32 / hnm_itemcf_topk_f32 read (val(j -> i) over the
+ * history items j), so they serve it unchanged: score(u, i) = sum_j w_uj * sim(j -> i).
+ *
+ * seq_ptr int64[num_users + 1] / seq_item int32 / seq_day int32: the user -> event CSR
+ * (UserSequence's layout).  An event is a distinct (user, day, item); a user's events are sorted
+ * by (day ascending, item ascending), a later purchase has a larger day.  gap_q uint32[max_gap]
+ * (device memory like every other pointer): gap_q[g - 1] is the fixed-point weight of a pair g
+ * days apart, <= 32768 = 2^15 (the weight 1.0).
+ *
+ * Users with more than max_history events are dropped, as in ItemCF's fit; the counts below run
+ * over the kept users.  n[a] = the number of events of item a: item_count int64[num_items].
+ * T[a, b] = the sum of gap_q[t - s - 1] over all ordered pairs of events of one user, the first
+ * (a, day s), the second (b, day t), with 1 <= t - s <= max_gap; a != b is required unless
+ * repeat_buys is set; same-day pairs are co-occurrence, which is ItemCF's, and do not count.  For
+ * T[a, b] > 0
+ *   sim(a -> b) = (float)( (double)T / ( 32768.0 * ( sqrt((double)n_a * (double)n_b) + shrink ) ) )
+ * in float64 with one rounding per operation and no fma, rounded once to float32: the form of
+ * hnm_itemcf_fit_f32.  Row a of nbr_idx int32[num_items, N] / nbr_val f32[num_items, N] keeps its
+ * N best in (sim descending, b ascending) order and is padded with (-1, 0.0f).
+ *
+ * Exactness.  T is an integer in uint64.  With e_u(x) = the events of item x of user u, T[a, b] <=
+ * 2^15 * sum_u e_u(a) * e_u(b), and e_u(a) + e_u(b) <= max_history <= 65535 gives e_u(a) * e_u(b)
+ * <= (65535 / 4) * (e_u(a) + e_u(b)), so T <= 2^15 * (65535 / 4) * E for a sequence of E events.
+ * The entry refuses E >= 2^31 (HNM_EUNSUPPORTED), so T < 2^60 (a -> a under repeat_buys: e (e - 1)
+ * / 2 pairs a user, T < 2^61): nothing overflows, integer sums are order-free, and the result is the same bits on every run and at every `window`.  That bound is
+ * why max_history has a ceiling here and not in ItemCF, whose counters add at most 2^30 a user.
+ *
+ * Ranges, checked before anything is launched (HNM_EINVAL, outputs untouched): 1 <= N <= 64;
+ * shrink finite and >= 0; 1 <= max_history <= 65535; 1 <= max_gap <= 1024; every gap_q entry <=
+ * 32768 (the table is read back: one stream sync, shared with the CSR's last offset);
+ * repeat_buys 0 or 1; `window`, below.  An item id outside [0, num_items) and a row outside the
+ * CSR raise the ctx error word (HNM_EOOB from hnm_ctx_check) and are skipped.  Days that do not
+ * ascend inside a row give an unspecified table; nothing outside the outputs is written.
+ *
+ * Two routes, the same T and so the same bits.  A row a whose events are followed, inside max_gap
+ * days, by at most 1,024 later events in all (same-item and zero-weight ones included: an upper
+ * bound of its distinct successors) is counted in an LDS hash table keyed by b.  Any other row
+ * walks the catalogue in windows of uint64 LDS counters and re-reads its ranges once a window:
+ * `window` = counters per pass, 0 = default 16,384 (128 KiB of LDS and the gap table: one
+ * workgroup a CU), else a multiple of 64 in [64, 16384].  Workspace: 12 bytes per event and 16 per
+ * item.  num_items = 0: HNM_OK, nothing launched.  Users and num_items: < 2^31. */
+hnm_status hnm_seqcf_fit_f32(hnm_ctx* ctx, const int64_t* seq_ptr, const int32_t* seq_item,
+                             const int32_t* seq_day, int64_t num_users, int64_t num_items, int N,
+                             double shrink, int64_t max_history, int max_gap,
+                             const uint32_t* gap_q, int repeat_buys, int window, int32_t* nbr_idx,
+                             float* nbr_val, int64_t* item_count);
+
 /* ---- Fusion of overlapping top-K lists: an ensemble of models (no reference counterpart) ----
  * hnm_topk_merge_f32 merges lists whose items are disjoint.  Here G models each give a list per
  * row, the same item may stand in several of them, and its fused score depends on every list
